@@ -17,6 +17,12 @@ RCCL/xGMI (BASELINE config 4).  Weak scaling: per-GPU work is fixed as N
 grows.  Timed region: barrier + device sync on both sides, K steps, max over
 ranks; the gather's share is timed separately with events on the same stream.
 
+A plain run sets up, warms up, times the K steps and prints the line.  The
+legs that take runs of their own (the host C port as CPU baseline, the
+reference's one-pair host surface) run only with ``--full``.
+``--dump-outputs DIR`` writes what the last timed step computed (rank 0: the
+int16 disparity maps of the whole batch, as float32) to ``DIR/<name>.npy``.
+
 Prints ONE JSON line on rank 0 (DESIGN.md §6 lists every field).  The
 roofline figure follows SURVEY.md §8(d): the model's bytes attributable to
 the dominant kernel (see ``model_stage_bytes``) over that kernel's average
@@ -82,14 +88,20 @@ def parse():
     ap.add_argument("--tune", default="",
                     help="launch-shape knobs for A/B measurements, e.g. ew_waves=1,ew_lanes=16 "
                          "(sm_set_tuning; every value gives the same disparities)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: the CPU baseline on the host C port and "
+                         "the reference's host surface (--cpu-baseline-pairs, --host-surface-calls)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last of them computed as DIR/<name>.npy (float32; "
+                         "a fixed seeded sample where the arrays exceed 64 MB in all)")
     ap.add_argument("--cpu-baseline-pairs", type=int, default=8,
-                    help="pairs timed on the host C port per thread (rank 0, N=1 only); 0 = skip")
+                    help="--full: pairs timed on the host C port per thread (rank 0, N=1 only); 0 = skip")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="host threads for the multi-core CPU baseline; 0 = the process's CPU share "
                          "(cpu_share(): OMP_NUM_THREADS where the pool sets it, else the affinity mask)")
     ap.add_argument("--host-surface-calls", type=int, default=20,
-                    help="rank 0, N=1: timed calls of the reference surface compute_disparity (host numpy in/out, "
-                         "settings.ini, KITTI size); 0 = skip")
+                    help="--full, rank 0, N=1: timed calls of the reference surface compute_disparity (host numpy "
+                         "in/out, settings.ini, KITTI size); 0 = skip")
     ap.add_argument("--traffic-file", default=os.path.join(ROOT, "profiles", "traffic_latest.json"))
     ap.add_argument("--valu-file", default=os.path.join(ROOT, "profiles", "valu_latest.json"))
     ap.add_argument("--selftest-cpu", action="store_true",
@@ -272,7 +284,7 @@ class GpuWorkload:
         # not just run the batch workload: the state a one-pair caller sees (after the 8-pair
         # bench the same calls measured 12 % slower on one box: 1.09 vs 0.97 ms)
         self.hs = None
-        if (int(os.environ.get("WORLD_SIZE", "1")) == 1 and self.args.host_surface_calls > 0
+        if (self.args.full and int(os.environ.get("WORLD_SIZE", "1")) == 1 and self.args.host_surface_calls > 0
                 and self.args.config == "kitti"):
             self.hs = host_surface(self.args, self.local_rank)
 
@@ -401,6 +413,14 @@ class GpuWorkload:
         c1 = self.eng.counters()
         self.timed_counters = {k: c1[k] - self._ct0[k] for k in c1}
 
+    def outputs(self, disp):
+        """What a caller of the timed path receives from a step: the disparity maps ``disp``
+        (disparity5: also the right matcher's maps and the WLS-filtered maps of this rank)."""
+        out = {"disparity": disp}
+        if self.full:
+            out.update(disparity_right=self.dOutR, disparity_filtered=self.dFilt)
+        return out
+
     def report(self, elapsed, K, gpairs, world):
         """The bench line's workload-specific fields (rank 0)."""
         args, H, W, D, P = self.args, self.H, self.W, self.D, self.P
@@ -478,7 +498,7 @@ class GpuWorkload:
         hs_pair = None
         if world == 1 and self.hs is not None:
             line["host_surface"], hs_pair = self.hs
-        if world == 1 and args.cpu_baseline_pairs > 0:
+        if args.full and world == 1 and args.cpu_baseline_pairs > 0:
             line["cpu_baseline"] = cpu_baseline(args, H, W, D, self.p, self.lefts, self.rights, out0, self.volume,
                                                 self.full, hs_pair)
         return line
@@ -543,6 +563,9 @@ class StandInWorkload:
 
     def timed_end(self):
         pass
+
+    def outputs(self, disp):
+        return {"disparity": disp}
 
     def report(self, elapsed, K, gpairs, world):
         return {"value": None, "dtype": None,
@@ -624,6 +647,8 @@ def run_rank(args, wl, world, rank):
     t1 = time.perf_counter()
     wl.timed_end()
     elapsed = t1 - t0
+    if args.dump_outputs and rank == 0:  # the last timed step's maps (gathered: of every rank)
+        dump_outputs(args.dump_outputs, wl.outputs(wl.out if og is None else og.result(nstep[0] - 1)))
     gather_ms = gather_exposed_ms = 0.0
     if og is not None:
         gather_ms, gather_exposed_ms = og.transfer_ms(), og.exposed_ms()
@@ -687,6 +712,25 @@ def run_rank(args, wl, world, rank):
         print(json.dumps(line), flush=True)
     if dist_on:
         dist.destroy_process_group()
+
+
+DUMP_MAX_BYTES = 63 * 10 ** 6  # array bytes per dump: under 64 MB with the .npy headers
+
+
+def dump_outputs(path, arrays):
+    """Write each array as ``path/<name>.npy`` in float32.  Where they exceed DUMP_MAX_BYTES in
+    all, every array is cut to the same fixed sample of its elements (flat indices drawn with
+    seed 0, sorted), so two runs with the same arguments write the same elements."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: v.cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.size for a in arrays.values()) * 4
+    for name, a in arrays.items():
+        a = a.astype(np.float32)
+        if total > DUMP_MAX_BYTES:
+            keep = a.size * DUMP_MAX_BYTES // total
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def design_kernels(args, stages, H, W, D, p, P_dirs, sweep, bm, lines=False, strips=0):

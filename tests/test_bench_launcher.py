@@ -77,6 +77,40 @@ def test_dist_flag_one_rank():
     assert d["distributed"]["gathered_in_pair_order"] is True
 
 
+def test_dump_outputs_writes_the_last_steps_maps(tmp_path):
+    # the stand-in step's maps are known per pair index (left image value x 16); two ranks, so
+    # the dump is the gathered batch of the last timed step
+    import numpy as np
+
+    out = tmp_path / "dump"
+    r = _run(["--gpus", "2", "--selftest-cpu", "--steps", "3", "--warmup", "1", "--config", "tsukuba",
+              "--pairs-per-gpu", "2", "--dump-outputs", str(out)])
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = _json_line(r.stdout)
+    assert d["steps"] == 3 and d["ms_per_step"] > 0
+    assert sorted(os.listdir(out)) == ["disparity.npy"]
+    a = np.load(out / "disparity.npy")
+    assert a.dtype == np.float32 and a.shape == (4, 288, 384)
+    assert all((a[i] == i * 16).all() for i in range(4))
+
+
+def test_dump_outputs_samples_above_the_size_cap(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4000)
+    arrays = {"a": torch.arange(3000, dtype=torch.int16).reshape(30, 100), "b": torch.ones(1000, dtype=torch.int16)}
+    bench.dump_outputs(str(tmp_path / "x"), arrays)
+    bench.dump_outputs(str(tmp_path / "y"), arrays)
+    a, b = np.load(tmp_path / "x" / "a.npy"), np.load(tmp_path / "x" / "b.npy")
+    assert a.dtype == b.dtype == np.float32 and a.shape == (750,) and b.shape == (250,)
+    assert (np.diff(a) > 0).all() and a.max() < 3000  # distinct elements of the array, in order
+    assert np.array_equal(a, np.load(tmp_path / "y" / "a.npy"))  # the same sample every run
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 16000)
+    bench.dump_outputs(str(tmp_path / "z"), arrays)
+    assert np.array_equal(np.load(tmp_path / "z" / "a.npy"), np.arange(3000, dtype=np.float32).reshape(30, 100))
+
+
 def test_metric_names_the_config():
     assert bench.metric_for("kitti") == json.load(open(os.path.join(ROOT, "BASELINE.json")))["metric"]
     assert "Middlebury" in bench.metric_for("middlebury") and "2880×1988 D=256" in bench.metric_for("middlebury")

@@ -34,13 +34,13 @@ if [ "$PART" = A ] || [ "$PART" = T ] || [ "$PART" = P ]; then
   cp "$OUT/census8_valu.json" profiles/valu_latest.json
   [ "$PART" = A ] && step valu_rate 120 ./tools/ubench/valu_rate
   [ "$PART" = A ] && FLAGS=0 step single 400 bash tools/gpu_single.sh $TAG
-  step bench 400 python -u bench.py --traffic-file "$OUT/census8_traffic.json"
-  step bench_sgbm5 400 python -u bench.py --mode sgbm5 --traffic-file "$OUT/sgbm5_traffic.json" --valu-file "$OUT/sgbm5_valu.json"
+  step bench 400 python -u bench.py --full --traffic-file "$OUT/census8_traffic.json"
+  step bench_sgbm5 400 python -u bench.py --full --mode sgbm5 --traffic-file "$OUT/sgbm5_traffic.json" --valu-file "$OUT/sgbm5_valu.json"
   step bench_middlebury 400 python -u bench.py --config middlebury --pairs-per-gpu 4 --steps 40 --warmup 4 --cpu-baseline-pairs 0 --host-surface-calls 0 --traffic-file "$OUT/middlebury_traffic.json" --valu-file "$OUT/middlebury_valu.json"
 else
   step bench_census8_perdir 300 python -u bench.py --engine perdir --cpu-baseline-pairs 0 --host-surface-calls 0
   step bench_sgbm5_perdir 300 python -u bench.py --mode sgbm5 --engine perdir --cpu-baseline-pairs 0 --host-surface-calls 0
-  for m in sgbm8 volume8 disparity5 bm; do step bench_$m 300 python -u bench.py --mode $m --host-surface-calls 0; done
-  step bench_tsukuba 300 python -u bench.py --config tsukuba --mode sgbm5 --host-surface-calls 0
+  for m in sgbm8 volume8 disparity5 bm; do step bench_$m 300 python -u bench.py --full --mode $m --host-surface-calls 0; done
+  step bench_tsukuba 300 python -u bench.py --full --config tsukuba --mode sgbm5 --host-surface-calls 0
 fi
 echo done
