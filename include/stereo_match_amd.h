@@ -209,6 +209,42 @@ int sm_reproject_image_to_3d(sm_ctx* ctx, const void* disp, int disp_type, int H
 int sm_reproject_image_to_3d_device(sm_ctx* ctx, const void* d_disp, int disp_type, int nimg, int H, int W,
                                     const double* Q, int handle_missing, float* d_xyz);
 
+/* ---- Rectification front end: the reference's rectify_opencv
+ * (disparity_calculation.py:131-210: cv2.initUndistortRectifyMap x2, cv2.remap(INTER_LINEAR) x2)
+ * and the two cv2.cvtColor(COLOR_BGR2GRAY) calls after it (:286-287).  The arithmetic is
+ * stated in DESIGN.md §4.7 (version-scoped restatements; parity with OpenCV unpinned).
+ * Image sizes (source and destination) are 1..16384 per side; anything else is SM_E_ARG. */
+typedef struct sm_rectify_cam {
+    double K[9];    /* camera matrix, row-major: fx = K[0], fy = K[4], cx = K[2], cy = K[5]; skew ignored */
+    double dist[5]; /* (k1, k2, p1, p2, k3), OpenCV order */
+    double iR[9];   /* inv(P[:3,:3] @ R), row-major, computed by the caller in float64 */
+} sm_rectify_cam;
+
+/* initUndistortRectifyMap(K, dist, R, P, (W, H), CV_32FC1): mapx / mapy float32 [H][W].
+ * Host version synchronous; the device version asynchronous. */
+int sm_rectify_map(sm_ctx* ctx, const sm_rectify_cam* cam, int H, int W, float* mapx, float* mapy);
+int sm_rectify_map_device(sm_ctx* ctx, const sm_rectify_cam* cam, int H, int W, float* d_mapx, float* d_mapy);
+
+/* remap(src, mapx, mapy, INTER_LINEAR), constant-0 border, on a uint8 image of `channels`
+ * (1 or 3) interleaved bytes per pixel, rows src_stride bytes apart (>= srcW*channels).
+ * dst (nullable): [H][W][channels], row stride W*channels.  gray (nullable; channels == 3):
+ * cvtColor(dst, COLOR_BGR2GRAY), [H][W], computed from the rounded uint8 BGR values.  At
+ * least one output.  Synchronous. */
+int sm_remap_u8(sm_ctx* ctx, const uint8_t* src, int srcH, int srcW, int src_stride, int channels,
+                const float* mapx, const float* mapy, int H, int W, uint8_t* dst, uint8_t* gray);
+/* Batch on device pointers: image i at d_src + i*img_stride_bytes, one map pair shared by
+ * the batch, outputs at d_dst + i*H*W*channels and d_gray + i*H*W.  Asynchronous. */
+int sm_remap_u8_batch_device(sm_ctx* ctx, const uint8_t* d_src, int nimg, size_t img_stride_bytes, int srcH, int srcW,
+                             int src_stride, int channels, const float* d_mapx, const float* d_mapy, int H, int W,
+                             uint8_t* d_dst, uint8_t* d_gray);
+
+/* cvtColor(src, COLOR_BGR2GRAY) alone on uint8 BGR images (rows src_stride bytes apart,
+ * >= 3*W): gray [H][W].  Host version synchronous; the device batch (image i at
+ * d_src + i*img_stride_bytes, gray at d_gray + i*H*W) asynchronous. */
+int sm_bgr2gray_u8(sm_ctx* ctx, const uint8_t* src, int H, int W, int src_stride, uint8_t* gray);
+int sm_bgr2gray_u8_batch_device(sm_ctx* ctx, const uint8_t* d_src, int nimg, size_t img_stride_bytes, int H, int W,
+                                int src_stride, uint8_t* d_gray);
+
 /* ---- StereoBM (the reference's method="BM" branch,
  * stereo_vision/stereo_vision.py:164-166: cv2.StereoBM_create(numDisparities,
  * blockSize)).  Fields follow cv::StereoBM's setters. */

@@ -6,6 +6,9 @@ Public surface (mirrors the reference / OpenCV names the reference uses):
 * :func:`StereoSGBM_create`, :func:`createRightMatcher` — the cv2 /
   cv2.ximgproc calls at ``stereo_vision/stereo_vision.py:153,171``
 * :func:`parse_config_file` — ``disparity_calculation.py:75``
+* :func:`rectify_opencv`, :func:`stereoRectify`, :func:`initUndistortRectifyMap`, :func:`remap`,
+  :func:`cvtColor`, :class:`StereoRectifier` — the rectification front end,
+  ``disparity_calculation.py:131-210,286-287``
 
 All compute runs in ``libstereo_match_amd.so`` (HIP, gfx950) through the
 C-ABI in ``include/stereo_match_amd.h``; there is no CPU fallback.
@@ -17,11 +20,15 @@ from .settings import DEFAULT_SETTINGS, parse_config_file
 from .stereo_vision import compute_disparity, matcher_from_settings
 from ._lib import SmError
 from .reproject import project_points_3D, reprojectImageTo3D, write_ply
+from .rectify import (CALIB_ZERO_DISPARITY, COLOR_BGR2GRAY, CV_32FC1, INTER_LINEAR, StereoRectifier, cvtColor,
+                      initUndistortRectifyMap, rectify_opencv, remap, stereoRectify)
 
 __all__ = [
     "compute_disparity", "matcher_from_settings", "StereoSGBM", "StereoSGBM_create", "createRightMatcher",
     "STEREO_SGBM_MODE_SGBM", "STEREO_SGBM_MODE_HH", "STEREO_SGBM_MODE_SGBM_3WAY", "STEREO_SGBM_MODE_HH4",
     "parse_config_file", "DEFAULT_SETTINGS", "SmError", "filterSpeckles", "reprojectImageTo3D",
     "project_points_3D", "write_ply", "StereoBM", "StereoBM_create",
+    "stereoRectify", "initUndistortRectifyMap", "remap", "cvtColor", "rectify_opencv", "StereoRectifier",
+    "CALIB_ZERO_DISPARITY", "CV_32FC1", "INTER_LINEAR", "COLOR_BGR2GRAY",
 ]
 __version__ = "0.1.0"

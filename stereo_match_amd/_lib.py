@@ -60,6 +60,11 @@ class SmBmParams(ctypes.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class SmRectifyCam(ctypes.Structure):
+    """Mirror of ``struct sm_rectify_cam``: K and iR row-major 3x3, dist = (k1, k2, p1, p2, k3)."""
+    _fields_ = [("K", ctypes.c_double * 9), ("dist", ctypes.c_double * 5), ("iR", ctypes.c_double * 9)]
+
+
 ABI_VERSION = 3  # include/stereo_match_amd.h SM_ABI_VERSION this binding is written against
 
 _c = ctypes
@@ -108,6 +113,17 @@ _SIGS = {
                                             _c.c_void_p, _c.c_int, _c.c_void_p]),
     "sm_reproject_image_to_3d_device": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
                                                    _c.c_void_p, _c.c_int, _c.c_void_p]),
+    "sm_rectify_map": (_c.c_int, [_c.c_void_p, _c.POINTER(SmRectifyCam), _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p]),
+    "sm_rectify_map_device": (_c.c_int, [_c.c_void_p, _c.POINTER(SmRectifyCam), _c.c_int, _c.c_int, _c.c_void_p,
+                                         _c.c_void_p]),
+    "sm_remap_u8": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p,
+                               _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p]),
+    "sm_remap_u8_batch_device": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_size_t, _c.c_int, _c.c_int,
+                                            _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int,
+                                            _c.c_void_p, _c.c_void_p]),
+    "sm_bgr2gray_u8": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p]),
+    "sm_bgr2gray_u8_batch_device": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_size_t, _c.c_int, _c.c_int,
+                                               _c.c_int, _c.c_void_p]),
     "sm_bm_default_params": (_c.c_int, [_c.c_int, _c.c_int, _c.POINTER(SmBmParams)]),
     "sm_bm_right_matcher_params": (_c.c_int, [_c.POINTER(SmBmParams), _c.POINTER(SmBmParams)]),
     "sm_bm_compute": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int,
@@ -424,6 +440,62 @@ class Engine:
         self._check(self._lib.sm_reproject_image_to_3d_device(self.ctx, ctypes.c_void_p(d_disp), kind, nimg, H, W,
                                                               Qd.ctypes.data, int(bool(handle_missing)),
                                                               ctypes.c_void_p(d_xyz)))
+
+    # -- rectification front end ------------------------------------------------------
+    def rectify_map(self, cam: "SmRectifyCam", H: int, W: int):
+        """initUndistortRectifyMap: float32 (mapx, mapy), each [H, W]."""
+        mapx = np.empty((max(H, 0), max(W, 0)), np.float32)
+        mapy = np.empty_like(mapx)
+        self._check(self._lib.sm_rectify_map(self.ctx, ctypes.byref(cam), H, W, mapx.ctypes.data, mapy.ctypes.data))
+        return mapx, mapy
+
+    def rectify_map_device(self, cam: "SmRectifyCam", H: int, W: int, d_mapx: int, d_mapy: int):
+        self._check(self._lib.sm_rectify_map_device(self.ctx, ctypes.byref(cam), H, W, ctypes.c_void_p(d_mapx),
+                                                    ctypes.c_void_p(d_mapy)))
+
+    def remap(self, src: np.ndarray, mapx: np.ndarray, mapy: np.ndarray, want_dst: bool = True,
+              want_gray: bool = False):
+        """remap(INTER_LINEAR) of a uint8 [h, w] or [h, w, 3] image (any row stride, pixels
+        contiguous) through float32 maps [H, W]: (dst or None, gray or None)."""
+        if src.dtype != np.uint8 or src.ndim not in (2, 3):
+            raise ValueError("remap: src must be a uint8 [h, w] or [h, w, c] array")
+        cn = 1 if src.ndim == 2 else src.shape[2]
+        if src.size and (src.strides[1] != cn or (src.ndim == 3 and src.strides[2] != 1) or src.strides[0] < 0):
+            src = np.ascontiguousarray(src)
+        mapx = np.ascontiguousarray(mapx, np.float32)
+        mapy = np.ascontiguousarray(mapy, np.float32)
+        if mapx.ndim != 2 or mapx.shape != mapy.shape:
+            raise ValueError("remap: mapx and mapy must be float32 [H, W] arrays of one shape")
+        H, W = mapx.shape
+        dst = np.empty((H, W) if src.ndim == 2 else (H, W, cn), np.uint8) if want_dst else None
+        gray = np.empty((H, W), np.uint8) if want_gray else None
+        self._check(self._lib.sm_remap_u8(
+            self.ctx, src.ctypes.data, src.shape[0], src.shape[1], src.strides[0] if src.size else 0, cn,
+            mapx.ctypes.data, mapy.ctypes.data, H, W, dst.ctypes.data if want_dst else None,
+            gray.ctypes.data if want_gray else None))
+        return dst, gray
+
+    def remap_batch_device(self, d_src: int, nimg: int, img_stride: int, srcH: int, srcW: int, src_stride: int,
+                           channels: int, d_mapx: int, d_mapy: int, H: int, W: int, d_dst, d_gray):
+        self._check(self._lib.sm_remap_u8_batch_device(
+            self.ctx, ctypes.c_void_p(d_src), nimg, img_stride, srcH, srcW, src_stride, channels,
+            ctypes.c_void_p(d_mapx), ctypes.c_void_p(d_mapy), H, W, ctypes.c_void_p(d_dst) if d_dst else None,
+            ctypes.c_void_p(d_gray) if d_gray else None))
+
+    def bgr2gray(self, src: np.ndarray) -> np.ndarray:
+        """cvtColor(COLOR_BGR2GRAY) of a uint8 [H, W, 3] image."""
+        if src.dtype != np.uint8 or src.ndim != 3 or src.shape[2] != 3:
+            raise ValueError("bgr2gray: src must be a uint8 [H, W, 3] array")
+        src = np.ascontiguousarray(src)
+        H, W = src.shape[:2]
+        gray = np.empty((H, W), np.uint8)
+        self._check(self._lib.sm_bgr2gray_u8(self.ctx, src.ctypes.data, H, W, 3 * W, gray.ctypes.data))
+        return gray
+
+    def bgr2gray_batch_device(self, d_src: int, nimg: int, img_stride: int, H: int, W: int, src_stride: int,
+                              d_gray: int):
+        self._check(self._lib.sm_bgr2gray_u8_batch_device(self.ctx, ctypes.c_void_p(d_src), nimg, img_stride, H, W,
+                                                          src_stride, ctypes.c_void_p(d_gray)))
 
     # -- StereoBM -------------------------------------------------------------------
     def bm_compute(self, left: np.ndarray, right: np.ndarray, params: "SmBmParams") -> np.ndarray:

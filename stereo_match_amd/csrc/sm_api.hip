@@ -32,6 +32,7 @@
 #include "sm_wls.hpp"
 #include "sm_speckle.hpp"
 #include "sm_reproject.hpp"
+#include "sm_rectify.hpp"
 #include "sm_bm.hpp"
 #include "sm_wide.hpp"
 #include "sm_sweep_host.hpp"
@@ -138,6 +139,7 @@ struct sm_ctx {
     hipStream_t stream = nullptr;  // stream A
     hipStream_t side = nullptr;    // stream B
     DevBuf img[2], planes, out, dbg, volbuf, sp_parent, sp_count, rp_in, rp_out, rp_min, bm_pre[2], bm_cost;
+    DevBuf rm_src, rm_mapx, rm_mapy, rm_dst, rm_gray;  // host-pointer rectify-map / remap / gray entry points
     DevBuf wls_num, wls_den, wls_inter, wls_w, wls_disp[2], wls_out;  // WLS scratch
     DevBuf wls_R, wls_IT;         // WLS: Thomas pivots / elimination factors of every pass
     hipStream_t wls_stream = nullptr;  // compute_disparity: WLS weights + pivots beside the matchers
@@ -2449,7 +2451,8 @@ void sm_destroy(sm_ctx* ctx)
                       &ctx->wls_disp[1], &ctx->wls_out, &ctx->sp_parent, &ctx->sp_count,
                       &ctx->rp_in,   &ctx->rp_out,  &ctx->rp_min,    &ctx->bm_pre[0],   &ctx->bm_pre[1],
                       &ctx->bm_cost, &ctx->hop,     &ctx->sweep_err, &ctx->wls_R,      &ctx->wls_IT,
-                      &ctx->volwin};
+                      &ctx->volwin,  &ctx->rm_src,  &ctx->rm_mapx,   &ctx->rm_mapy,     &ctx->rm_dst,
+                      &ctx->rm_gray};
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (auto& bs : ctx->set) {
@@ -2961,6 +2964,179 @@ int sm_reproject_image_to_3d(sm_ctx* ctx, const void* disp, int disp_type, int H
     }
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return check_sweep_errors(ctx);
+}
+
+// ---- rectification front end (sm_rectify.hpp)
+namespace {
+constexpr int kRectMaxDim = 16384;
+
+bool aligned_to(const void* p, size_t n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1)) == 0; }
+}  // namespace
+
+int sm_rectify_map_device(sm_ctx* ctx, const sm_rectify_cam* cam, int H, int W, float* d_mapx, float* d_mapy)
+{
+    if (!ctx) return fail(nullptr, SM_E_ARG, "ctx is NULL");
+    if (!cam || !d_mapx || !d_mapy) return fail(ctx, SM_E_ARG, "rectify map: NULL argument");
+    if (H <= 0 || W <= 0 || H > kRectMaxDim || W > kRectMaxDim)
+        return fail(ctx, SM_E_ARG, "rectify map: size %d x %d outside 1..%d", W, H, kRectMaxDim);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    smk::RectMapArgs a{};
+    std::memcpy(a.iR, cam->iR, sizeof a.iR);
+    a.k1 = cam->dist[0], a.k2 = cam->dist[1], a.p1 = cam->dist[2], a.p2 = cam->dist[3], a.k3 = cam->dist[4];
+    a.fx = cam->K[0], a.fy = cam->K[4], a.cx = cam->K[2], a.cy = cam->K[5];
+    a.mapx = d_mapx, a.mapy = d_mapy, a.H = H, a.W = W;
+    hipLaunchKernelGGL(smk::k_rectify_map, dim3((W + 255) / 256, H), dim3(256), 0, ctx->stream, a);
+    HIP_TRY(ctx, hipGetLastError());
+    return SM_OK;
+}
+
+int sm_rectify_map(sm_ctx* ctx, const sm_rectify_cam* cam, int H, int W, float* mapx, float* mapy)
+{
+    if (!ctx) return fail(nullptr, SM_E_ARG, "ctx is NULL");
+    if (!cam || !mapx || !mapy) return fail(ctx, SM_E_ARG, "rectify map: NULL argument");
+    if (H <= 0 || W <= 0 || H > kRectMaxDim || W > kRectMaxDim)
+        return fail(ctx, SM_E_ARG, "rectify map: size %d x %d outside 1..%d", W, H, kRectMaxDim);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t mb = (size_t)H * W * 4;
+    int rc;
+    if ((rc = ensure(ctx, ctx->rm_mapx, mb)) != SM_OK) return rc;
+    if ((rc = ensure(ctx, ctx->rm_mapy, mb)) != SM_OK) return rc;
+    if ((rc = sm_rectify_map_device(ctx, cam, H, W, (float*)ctx->rm_mapx.p, (float*)ctx->rm_mapy.p)) != SM_OK) return rc;
+    {
+        StageTimer t_(ctx, ctx->stream, SM_STAGE_D2H, 1);
+        HIP_TRY(ctx, hipMemcpyAsync(mapx, ctx->rm_mapx.p, mb, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(mapy, ctx->rm_mapy.p, mb, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return SM_OK;
+}
+
+namespace {
+int remap_check(sm_ctx* ctx, const void* src, int srcH, int srcW, int src_stride, int channels, const void* mapx,
+                const void* mapy, int H, int W, const void* dst, const void* gray)
+{
+    if (!src || !mapx || !mapy) return fail(ctx, SM_E_ARG, "remap: NULL source or map");
+    if (!dst && !gray) return fail(ctx, SM_E_ARG, "remap: both outputs are NULL");
+    if (channels != 1 && channels != 3) return fail(ctx, SM_E_ARG, "remap: channels %d (1 or 3)", channels);
+    if (gray && channels != 3) return fail(ctx, SM_E_ARG, "remap: the gray output needs a 3-channel (BGR) source");
+    if (srcH <= 0 || srcW <= 0 || srcH > kRectMaxDim || srcW > kRectMaxDim)
+        return fail(ctx, SM_E_ARG, "remap: source size %d x %d outside 1..%d", srcW, srcH, kRectMaxDim);
+    if (H <= 0 || W <= 0 || H > kRectMaxDim || W > kRectMaxDim)
+        return fail(ctx, SM_E_ARG, "remap: destination size %d x %d outside 1..%d", W, H, kRectMaxDim);
+    if (src_stride < srcW * channels) return fail(ctx, SM_E_ARG, "remap: src_stride %d < %d", src_stride, srcW * channels);
+    return SM_OK;
+}
+}  // namespace
+
+int sm_remap_u8_batch_device(sm_ctx* ctx, const uint8_t* d_src, int nimg, size_t img_stride_bytes, int srcH, int srcW,
+                             int src_stride, int channels, const float* d_mapx, const float* d_mapy, int H, int W,
+                             uint8_t* d_dst, uint8_t* d_gray)
+{
+    if (!ctx) return fail(nullptr, SM_E_ARG, "ctx is NULL");
+    int rc;
+    if ((rc = remap_check(ctx, d_src, srcH, srcW, src_stride, channels, d_mapx, d_mapy, H, W, d_dst, d_gray)) != SM_OK)
+        return rc;
+    if (nimg < 0 || nimg > 65535 * smk::REMAP_IPT) return fail(ctx, SM_E_ARG, "remap: nimg %d", nimg);
+    if (nimg > 1 && img_stride_bytes < (size_t)(srcH - 1) * src_stride + (size_t)srcW * channels)
+        return fail(ctx, SM_E_ARG, "remap: img_stride_bytes %zu smaller than one image", img_stride_bytes);
+    if (nimg == 0) return SM_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    smk::RemapArgs a{};
+    a.src = d_src, a.mapx = d_mapx, a.mapy = d_mapy, a.dst = d_dst, a.gray = d_gray;
+    a.img_stride = img_stride_bytes;
+    a.nimg = nimg, a.srcH = srcH, a.srcW = srcW, a.src_stride = src_stride, a.H = H, a.W = W;
+    a.Wq = (W + 3) / 4;
+    a.vec = W % 4 == 0 && aligned_to(d_mapx, 16) && aligned_to(d_mapy, 16) && aligned_to(d_dst, 4) &&
+            aligned_to(d_gray, 4);
+    const dim3 grid(((unsigned)H * a.Wq + 255) / 256, (nimg + smk::REMAP_IPT - 1) / smk::REMAP_IPT);
+    if (channels == 1)
+        hipLaunchKernelGGL((smk::k_remap_u8<1, false>), grid, dim3(256), 0, ctx->stream, a);
+    else if (d_gray)
+        hipLaunchKernelGGL((smk::k_remap_u8<3, true>), grid, dim3(256), 0, ctx->stream, a);
+    else
+        hipLaunchKernelGGL((smk::k_remap_u8<3, false>), grid, dim3(256), 0, ctx->stream, a);
+    HIP_TRY(ctx, hipGetLastError());
+    return SM_OK;
+}
+
+int sm_remap_u8(sm_ctx* ctx, const uint8_t* src, int srcH, int srcW, int src_stride, int channels, const float* mapx,
+                const float* mapy, int H, int W, uint8_t* dst, uint8_t* gray)
+{
+    if (!ctx) return fail(nullptr, SM_E_ARG, "ctx is NULL");
+    int rc;
+    if ((rc = remap_check(ctx, src, srcH, srcW, src_stride, channels, mapx, mapy, H, W, dst, gray)) != SM_OK) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t sb = (size_t)(srcH - 1) * src_stride + (size_t)srcW * channels, npx = (size_t)H * W;
+    if ((rc = ensure(ctx, ctx->rm_src, sb)) != SM_OK) return rc;
+    if ((rc = ensure(ctx, ctx->rm_mapx, npx * 4)) != SM_OK) return rc;
+    if ((rc = ensure(ctx, ctx->rm_mapy, npx * 4)) != SM_OK) return rc;
+    if (dst && (rc = ensure(ctx, ctx->rm_dst, npx * channels)) != SM_OK) return rc;
+    if (gray && (rc = ensure(ctx, ctx->rm_gray, npx)) != SM_OK) return rc;
+    {
+        StageTimer t_(ctx, ctx->stream, SM_STAGE_H2D, 1);
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->rm_src.p, src, sb, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->rm_mapx.p, mapx, npx * 4, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->rm_mapy.p, mapy, npx * 4, hipMemcpyHostToDevice, ctx->stream));
+    }
+    if ((rc = sm_remap_u8_batch_device(ctx, (const uint8_t*)ctx->rm_src.p, 1, 0, srcH, srcW, src_stride, channels,
+                                       (const float*)ctx->rm_mapx.p, (const float*)ctx->rm_mapy.p, H, W,
+                                       dst ? (uint8_t*)ctx->rm_dst.p : nullptr,
+                                       gray ? (uint8_t*)ctx->rm_gray.p : nullptr)) != SM_OK)
+        return rc;
+    {
+        StageTimer t_(ctx, ctx->stream, SM_STAGE_D2H, 1);
+        if (dst) HIP_TRY(ctx, hipMemcpyAsync(dst, ctx->rm_dst.p, npx * channels, hipMemcpyDeviceToHost, ctx->stream));
+        if (gray) HIP_TRY(ctx, hipMemcpyAsync(gray, ctx->rm_gray.p, npx, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return SM_OK;
+}
+
+int sm_bgr2gray_u8_batch_device(sm_ctx* ctx, const uint8_t* d_src, int nimg, size_t img_stride_bytes, int H, int W,
+                                int src_stride, uint8_t* d_gray)
+{
+    if (!ctx) return fail(nullptr, SM_E_ARG, "ctx is NULL");
+    if (!d_src || !d_gray) return fail(ctx, SM_E_ARG, "bgr2gray: NULL argument");
+    if (H <= 0 || W <= 0 || H > kRectMaxDim || W > kRectMaxDim)
+        return fail(ctx, SM_E_ARG, "bgr2gray: size %d x %d outside 1..%d", W, H, kRectMaxDim);
+    if (src_stride < W * 3) return fail(ctx, SM_E_ARG, "bgr2gray: src_stride %d < %d", src_stride, W * 3);
+    if (nimg < 0 || nimg > 65535) return fail(ctx, SM_E_ARG, "bgr2gray: nimg %d", nimg);
+    if (nimg > 1 && img_stride_bytes < (size_t)(H - 1) * src_stride + (size_t)W * 3)
+        return fail(ctx, SM_E_ARG, "bgr2gray: img_stride_bytes %zu smaller than one image", img_stride_bytes);
+    if (nimg == 0) return SM_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    smk::GrayArgs a{};
+    a.src = d_src, a.gray = d_gray, a.img_stride = img_stride_bytes, a.H = H, a.W = W, a.src_stride = src_stride;
+    hipLaunchKernelGGL(smk::k_bgr2gray, dim3((W + 255) / 256, H, nimg), dim3(256), 0, ctx->stream, a);
+    HIP_TRY(ctx, hipGetLastError());
+    return SM_OK;
+}
+
+int sm_bgr2gray_u8(sm_ctx* ctx, const uint8_t* src, int H, int W, int src_stride, uint8_t* gray)
+{
+    if (!ctx) return fail(nullptr, SM_E_ARG, "ctx is NULL");
+    if (!src || !gray) return fail(ctx, SM_E_ARG, "bgr2gray: NULL argument");
+    if (H <= 0 || W <= 0 || H > kRectMaxDim || W > kRectMaxDim)
+        return fail(ctx, SM_E_ARG, "bgr2gray: size %d x %d outside 1..%d", W, H, kRectMaxDim);
+    if (src_stride < W * 3) return fail(ctx, SM_E_ARG, "bgr2gray: src_stride %d < %d", src_stride, W * 3);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t sb = (size_t)(H - 1) * src_stride + (size_t)W * 3, npx = (size_t)H * W;
+    int rc;
+    if ((rc = ensure(ctx, ctx->rm_src, sb)) != SM_OK) return rc;
+    if ((rc = ensure(ctx, ctx->rm_gray, npx)) != SM_OK) return rc;
+    {
+        StageTimer t_(ctx, ctx->stream, SM_STAGE_H2D, 1);
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->rm_src.p, src, sb, hipMemcpyHostToDevice, ctx->stream));
+    }
+    if ((rc = sm_bgr2gray_u8_batch_device(ctx, (const uint8_t*)ctx->rm_src.p, 1, 0, H, W, src_stride,
+                                          (uint8_t*)ctx->rm_gray.p)) != SM_OK)
+        return rc;
+    {
+        StageTimer t_(ctx, ctx->stream, SM_STAGE_D2H, 1);
+        HIP_TRY(ctx, hipMemcpyAsync(gray, ctx->rm_gray.p, npx, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return SM_OK;
 }
 
 int sm_bm_default_params(int num_disparities, int block_size, sm_bm_params* out)
