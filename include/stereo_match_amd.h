@@ -245,6 +245,25 @@ int sm_bgr2gray_u8(sm_ctx* ctx, const uint8_t* src, int H, int W, int src_stride
 int sm_bgr2gray_u8_batch_device(sm_ctx* ctx, const uint8_t* d_src, int nimg, size_t img_stride_bytes, int H, int W,
                                 int src_stride, uint8_t* d_gray);
 
+/* ---- fastNlMeansDenoising(src, None, h, templateWindowSize, searchWindowSize) on uint8 gray
+ * images: the call in front of the matcher in the reference's test flow
+ * (disparity_test.py:94-95).  NORM_L2, one channel; the arithmetic is stated in DESIGN.md §4.8
+ * (a version-scoped restatement; parity with OpenCV unpinned).  templateWindowSize 1..9 and
+ * searchWindowSize 1..35 (an even size counts as the next odd one; larger: SM_E_UNSUPPORTED),
+ * any finite h >= 0, H and W 1..16384, rows src_stride bytes apart (>= W); anything else is
+ * SM_E_ARG.  The output is [H][W], densely packed.  Synchronous. */
+int sm_nlm_denoise_u8(sm_ctx* ctx, const uint8_t* src, int H, int W, int src_stride, float h, int template_window,
+                      int search_window, uint8_t* dst);
+/* Image i at d_src + i*img_stride_bytes, output at d_dst + i*H*W; one launch for the batch.
+ * Asynchronous, on the ctx stream (the first call with a new (h, template, search) builds and
+ * uploads the weight table and waits for that upload). */
+int sm_nlm_denoise_u8_batch_device(sm_ctx* ctx, const uint8_t* d_src, int nimg, size_t img_stride_bytes, int H, int W,
+                                   int src_stride, float h, int template_window, int search_window, uint8_t* d_dst);
+/* The weight table the calls above use: fills tab[0..*n), returns the fixed-point weight of
+ * distance 0 (fpm) and the shift applied to a patch distance before the lookup; tab may be NULL
+ * to query n.  Needs no context and no device. */
+int sm_nlm_weight_table(float h, int template_window, int search_window, int32_t* tab, int* n, int* fpm, int* shift);
+
 /* ---- StereoBM (the reference's method="BM" branch,
  * stereo_vision/stereo_vision.py:164-166: cv2.StereoBM_create(numDisparities,
  * blockSize)).  Fields follow cv::StereoBM's setters. */

@@ -9,6 +9,8 @@ Public surface (mirrors the reference / OpenCV names the reference uses):
 * :func:`rectify_opencv`, :func:`stereoRectify`, :func:`initUndistortRectifyMap`, :func:`remap`,
   :func:`cvtColor`, :class:`StereoRectifier` — the rectification front end,
   ``disparity_calculation.py:131-210,286-287``
+* :func:`fastNlMeansDenoising` — the denoiser in front of the matcher in the test flow,
+  ``disparity_test.py:94-95``
 
 All compute runs in ``libstereo_match_amd.so`` (HIP, gfx950) through the
 C-ABI in ``include/stereo_match_amd.h``; there is no CPU fallback.
@@ -22,6 +24,7 @@ from ._lib import SmError
 from .reproject import project_points_3D, reprojectImageTo3D, write_ply
 from .rectify import (CALIB_ZERO_DISPARITY, COLOR_BGR2GRAY, CV_32FC1, INTER_LINEAR, StereoRectifier, cvtColor,
                       initUndistortRectifyMap, rectify_opencv, remap, stereoRectify)
+from .denoise import fastNlMeansDenoising
 
 __all__ = [
     "compute_disparity", "matcher_from_settings", "StereoSGBM", "StereoSGBM_create", "createRightMatcher",
@@ -29,6 +32,6 @@ __all__ = [
     "parse_config_file", "DEFAULT_SETTINGS", "SmError", "filterSpeckles", "reprojectImageTo3D",
     "project_points_3D", "write_ply", "StereoBM", "StereoBM_create",
     "stereoRectify", "initUndistortRectifyMap", "remap", "cvtColor", "rectify_opencv", "StereoRectifier",
-    "CALIB_ZERO_DISPARITY", "CV_32FC1", "INTER_LINEAR", "COLOR_BGR2GRAY",
+    "CALIB_ZERO_DISPARITY", "CV_32FC1", "INTER_LINEAR", "COLOR_BGR2GRAY", "fastNlMeansDenoising",
 ]
 __version__ = "0.1.0"

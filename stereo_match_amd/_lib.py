@@ -124,6 +124,12 @@ _SIGS = {
     "sm_bgr2gray_u8": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p]),
     "sm_bgr2gray_u8_batch_device": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_size_t, _c.c_int, _c.c_int,
                                                _c.c_int, _c.c_void_p]),
+    "sm_nlm_denoise_u8": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_float, _c.c_int,
+                                     _c.c_int, _c.c_void_p]),
+    "sm_nlm_denoise_u8_batch_device": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_size_t, _c.c_int, _c.c_int,
+                                                  _c.c_int, _c.c_float, _c.c_int, _c.c_int, _c.c_void_p]),
+    "sm_nlm_weight_table": (_c.c_int, [_c.c_float, _c.c_int, _c.c_int, _c.c_void_p, _c.POINTER(_c.c_int),
+                                       _c.POINTER(_c.c_int), _c.POINTER(_c.c_int)]),
     "sm_bm_default_params": (_c.c_int, [_c.c_int, _c.c_int, _c.POINTER(SmBmParams)]),
     "sm_bm_right_matcher_params": (_c.c_int, [_c.POINTER(SmBmParams), _c.POINTER(SmBmParams)]),
     "sm_bm_compute": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int,
@@ -496,6 +502,46 @@ class Engine:
                               d_gray: int):
         self._check(self._lib.sm_bgr2gray_u8_batch_device(self.ctx, ctypes.c_void_p(d_src), nimg, img_stride, H, W,
                                                           src_stride, ctypes.c_void_p(d_gray)))
+
+    # -- fastNlMeansDenoising -------------------------------------------------------------
+    def nlm_denoise(self, src: np.ndarray, h: float, template_window: int, search_window: int,
+                    dst: np.ndarray = None) -> np.ndarray:
+        """fastNlMeansDenoising of a uint8 [H, W] image (any row stride, pixels contiguous);
+        ``dst`` (uint8 [H, W], C-contiguous) is filled and returned when given."""
+        if not isinstance(src, np.ndarray) or src.dtype != np.uint8 or src.ndim != 2:
+            raise ValueError("nlm_denoise: src must be a uint8 [H, W] array")
+        if src.size and (src.strides[1] != 1 or src.strides[0] < src.shape[1]):
+            src = np.ascontiguousarray(src)
+        H, W = src.shape
+        if dst is None:
+            dst = np.empty((H, W), np.uint8)
+        elif (not isinstance(dst, np.ndarray) or dst.dtype != np.uint8 or dst.shape != (H, W)
+              or not dst.flags.c_contiguous or not dst.flags.writeable):
+            raise ValueError(f"nlm_denoise: dst must be a writeable C-contiguous uint8 [{H}, {W}] array")
+        self._check(self._lib.sm_nlm_denoise_u8(self.ctx, src.ctypes.data if src.size else None, H, W,
+                                                src.strides[0] if src.size else W, float(h), int(template_window),
+                                                int(search_window), dst.ctypes.data if dst.size else None))
+        return dst
+
+    def nlm_denoise_batch_device(self, d_src: int, nimg: int, img_stride: int, H: int, W: int, src_stride: int,
+                                 h: float, template_window: int, search_window: int, d_dst: int):
+        self._check(self._lib.sm_nlm_denoise_u8_batch_device(
+            self.ctx, ctypes.c_void_p(d_src), nimg, img_stride, H, W, src_stride, float(h), int(template_window),
+            int(search_window), ctypes.c_void_p(d_dst)))
+
+    def nlm_weight_table(self, h: float, template_window: int, search_window: int):
+        """(tab int32 [n], fpm, shift): the weight table nlm_denoise uses (sm_nlm_weight_table)."""
+        n, fpm, shift = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        args = (float(h), int(template_window), int(search_window))
+        rc = self._lib.sm_nlm_weight_table(*args, None, ctypes.byref(n), ctypes.byref(fpm), ctypes.byref(shift))
+        if rc != SM_OK:
+            _raise(rc, None)  # a context-free call: the message is the thread's
+        tab = np.empty(n.value, np.int32)
+        rc = self._lib.sm_nlm_weight_table(*args, tab.ctypes.data, ctypes.byref(n), ctypes.byref(fpm),
+                                           ctypes.byref(shift))
+        if rc != SM_OK:
+            _raise(rc, None)
+        return tab, fpm.value, shift.value
 
     # -- StereoBM -------------------------------------------------------------------
     def bm_compute(self, left: np.ndarray, right: np.ndarray, params: "SmBmParams") -> np.ndarray:

@@ -33,6 +33,7 @@
 #include "sm_speckle.hpp"
 #include "sm_reproject.hpp"
 #include "sm_rectify.hpp"
+#include "sm_nlm.hpp"
 #include "sm_bm.hpp"
 #include "sm_wide.hpp"
 #include "sm_sweep_host.hpp"
@@ -140,6 +141,12 @@ struct sm_ctx {
     hipStream_t side = nullptr;    // stream B
     DevBuf img[2], planes, out, dbg, volbuf, sp_parent, sp_count, rp_in, rp_out, rp_min, bm_pre[2], bm_cost;
     DevBuf rm_src, rm_mapx, rm_mapy, rm_dst, rm_gray;  // host-pointer rectify-map / remap / gray entry points
+    // fastNlMeansDenoising: the non-zero prefix of the weight table on the device, cached for the
+    // (h, t, s) it was built for; its host copy lives here too, so it outlives the upload
+    DevBuf nlm_tab;
+    std::vector<int32_t> nlm_tab_host;
+    uint32_t nlm_key_h = 0;
+    int nlm_key_t = 0, nlm_key_s = 0, nlm_ntab = 0, nlm_shift = 0;
     DevBuf wls_num, wls_den, wls_inter, wls_w, wls_disp[2], wls_out;  // WLS scratch
     DevBuf wls_R, wls_IT;         // WLS: Thomas pivots / elimination factors of every pass
     hipStream_t wls_stream = nullptr;  // compute_disparity: WLS weights + pivots beside the matchers
@@ -2452,7 +2459,7 @@ void sm_destroy(sm_ctx* ctx)
                       &ctx->rp_in,   &ctx->rp_out,  &ctx->rp_min,    &ctx->bm_pre[0],   &ctx->bm_pre[1],
                       &ctx->bm_cost, &ctx->hop,     &ctx->sweep_err, &ctx->wls_R,      &ctx->wls_IT,
                       &ctx->volwin,  &ctx->rm_src,  &ctx->rm_mapx,   &ctx->rm_mapy,     &ctx->rm_dst,
-                      &ctx->rm_gray};
+                      &ctx->rm_gray, &ctx->nlm_tab};
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (auto& bs : ctx->set) {
@@ -3134,6 +3141,156 @@ int sm_bgr2gray_u8(sm_ctx* ctx, const uint8_t* src, int H, int W, int src_stride
     {
         StageTimer t_(ctx, ctx->stream, SM_STAGE_D2H, 1);
         HIP_TRY(ctx, hipMemcpyAsync(gray, ctx->rm_gray.p, npx, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return SM_OK;
+}
+
+// ---- fastNlMeansDenoising (sm_nlm.hpp)
+namespace {
+struct NlmGeo {
+    int th, sh, t, s, fpm, shift, n;
+    double mult;
+};
+
+// window sizes and h checked, and the table's constants (the only floating-point part)
+int nlm_geo(sm_ctx* ctx, float h, int template_window, int search_window, NlmGeo& g)
+{
+    if (template_window < 1) return fail(ctx, SM_E_ARG, "nlm: templateWindowSize %d < 1", template_window);
+    if (search_window < 1) return fail(ctx, SM_E_ARG, "nlm: searchWindowSize %d < 1", search_window);
+    if (!(h >= 0.f) || std::isinf(h)) return fail(ctx, SM_E_ARG, "nlm: h = %g (a finite h >= 0 is needed)", (double)h);
+    g.th = template_window / 2, g.sh = search_window / 2;
+    g.t = 2 * g.th + 1, g.s = 2 * g.sh + 1;
+    if (g.th > smk::NLM_MAX_TH)
+        return fail(ctx, SM_E_UNSUPPORTED, "nlm: templateWindowSize %d (template %d x %d) not built: 1..%d",
+                    template_window, g.t, g.t, 2 * smk::NLM_MAX_TH + 1);
+    if (g.sh > smk::NLM_MAX_SH)
+        return fail(ctx, SM_E_UNSUPPORTED, "nlm: searchWindowSize %d (search %d x %d) not built: 1..%d", search_window,
+                    g.s, g.s, 2 * smk::NLM_MAX_SH + 1);
+    g.fpm = INT32_MAX / (g.s * g.s * 255);
+    g.shift = 0;
+    while ((1 << g.shift) < g.t * g.t) g.shift++;
+    g.mult = double(1 << g.shift) / double(g.t * g.t);
+    g.n = int(65025.0 / g.mult + 1);
+    return SM_OK;
+}
+
+// tab[a] = rint(fpm * exp(-(a * mult) / (h * h))) (h * h in float32; a NaN weight, h = 0 at
+// a = 0, counts as 1), entries below fpm / 1000 zeroed; returns the non-zero prefix's length
+int nlm_table(const NlmGeo& g, float h, int32_t* tab)
+{
+    const float hhf = h * h;
+    const double hh = (double)hhf, floor_w = 0.001 * g.fpm;
+    int last = 0;
+    for (int a = 0; a < g.n; a++) {
+        double w = std::exp(-(a * g.mult) / hh);
+        if (w != w) w = 1.0;
+        int v = (int)std::nearbyint(g.fpm * w);  // the default rounding mode: half to even
+        if (v < floor_w) v = 0;
+        tab[a] = v;
+        if (v) last = a + 1;
+    }
+    return last;
+}
+
+// the device copy of the table's non-zero prefix for (h, t, s), cached in the context
+int ensure_nlm_table(sm_ctx* ctx, const NlmGeo& g, float h)
+{
+    uint32_t hb;
+    std::memcpy(&hb, &h, 4);
+    if (ctx->nlm_ntab > 0 && ctx->nlm_key_h == hb && ctx->nlm_key_t == g.t && ctx->nlm_key_s == g.s) return SM_OK;
+    // launches that read the old table (on whichever stream they were queued) finish first
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    ctx->nlm_ntab = 0;
+    ctx->nlm_tab_host.resize(g.n);
+    const int ntab = nlm_table(g, h, ctx->nlm_tab_host.data());
+    int rc;
+    if ((rc = ensure(ctx, ctx->nlm_tab, (size_t)ntab * 4)) != SM_OK) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->nlm_tab.p, ctx->nlm_tab_host.data(), (size_t)ntab * 4, hipMemcpyHostToDevice,
+                                ctx->stream));
+    // once per (h, t, s): the table is complete before a launch on any other stream uses it,
+    // and nlm_tab_host (kept anyway) is not touched while the copy runs
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->nlm_key_h = hb, ctx->nlm_key_t = g.t, ctx->nlm_key_s = g.s, ctx->nlm_shift = g.shift;
+    ctx->nlm_ntab = ntab;
+    return SM_OK;
+}
+
+int nlm_image_check(sm_ctx* ctx, const void* src, const void* dst, int H, int W, int src_stride)
+{
+    if (H <= 0 || W <= 0 || H > kRectMaxDim || W > kRectMaxDim)
+        return fail(ctx, SM_E_ARG, "nlm: size %d x %d outside 1..%d", W, H, kRectMaxDim);
+    if (!src || !dst) return fail(ctx, SM_E_ARG, "nlm: NULL argument");
+    if (src_stride < W) return fail(ctx, SM_E_ARG, "nlm: src_stride %d < %d", src_stride, W);
+    return SM_OK;
+}
+}  // namespace
+
+int sm_nlm_weight_table(float h, int template_window, int search_window, int32_t* tab, int* n, int* fpm, int* shift)
+{
+    NlmGeo g;
+    int rc;
+    if ((rc = nlm_geo(nullptr, h, template_window, search_window, g)) != SM_OK) return rc;
+    if (n) *n = g.n;
+    if (fpm) *fpm = g.fpm;
+    if (shift) *shift = g.shift;
+    if (tab) nlm_table(g, h, tab);
+    return SM_OK;
+}
+
+int sm_nlm_denoise_u8_batch_device(sm_ctx* ctx, const uint8_t* d_src, int nimg, size_t img_stride_bytes, int H, int W,
+                                   int src_stride, float h, int template_window, int search_window, uint8_t* d_dst)
+{
+    if (!ctx) return fail(nullptr, SM_E_ARG, "ctx is NULL");
+    int rc;
+    NlmGeo g;
+    if ((rc = nlm_image_check(ctx, d_src, d_dst, H, W, src_stride)) != SM_OK) return rc;
+    if ((rc = nlm_geo(ctx, h, template_window, search_window, g)) != SM_OK) return rc;
+    if (nimg < 0 || nimg > 65535) return fail(ctx, SM_E_ARG, "nlm: nimg %d", nimg);
+    if (nimg > 1 && img_stride_bytes < (size_t)(H - 1) * src_stride + (size_t)W)
+        return fail(ctx, SM_E_ARG, "nlm: img_stride_bytes %zu smaller than one image", img_stride_bytes);
+    if (nimg == 0) return SM_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if ((rc = ensure_nlm_table(ctx, g, h)) != SM_OK) return rc;
+    smk::NlmArgs a{};
+    a.src = d_src, a.dst = d_dst, a.tab = (const int32_t*)ctx->nlm_tab.p;
+    a.img_stride = img_stride_bytes;
+    a.H = H, a.W = W, a.src_stride = src_stride;
+    a.sh = g.sh, a.shift = ctx->nlm_shift, a.ntab = ctx->nlm_ntab;
+    a.pitch = smk::nlm_pitch(g.th, g.sh);
+    const bool lds_tab = a.ntab <= smk::NLM_LDS_TAB_MAX;
+    const size_t lds = smk::nlm_lds_bytes(g.th, g.sh, lds_tab ? a.ntab : 0);
+    const dim3 grid((W + smk::NLM_TILE - 1) / smk::NLM_TILE, (H + smk::NLM_TILE - 1) / smk::NLM_TILE, nimg);
+    if (lds_tab)
+        smk::nlm_launch<true>(g.th, grid, lds, ctx->stream, a);
+    else
+        smk::nlm_launch<false>(g.th, grid, lds, ctx->stream, a);
+    HIP_TRY(ctx, hipGetLastError());
+    return SM_OK;
+}
+
+int sm_nlm_denoise_u8(sm_ctx* ctx, const uint8_t* src, int H, int W, int src_stride, float h, int template_window,
+                      int search_window, uint8_t* dst)
+{
+    if (!ctx) return fail(nullptr, SM_E_ARG, "ctx is NULL");
+    int rc;
+    NlmGeo g;
+    if ((rc = nlm_image_check(ctx, src, dst, H, W, src_stride)) != SM_OK) return rc;
+    if ((rc = nlm_geo(ctx, h, template_window, search_window, g)) != SM_OK) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t sb = (size_t)(H - 1) * src_stride + (size_t)W, npx = (size_t)H * W;
+    if ((rc = ensure(ctx, ctx->rm_src, sb)) != SM_OK) return rc;
+    if ((rc = ensure(ctx, ctx->rm_gray, npx)) != SM_OK) return rc;
+    {
+        StageTimer t_(ctx, ctx->stream, SM_STAGE_H2D, 1);
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->rm_src.p, src, sb, hipMemcpyHostToDevice, ctx->stream));
+    }
+    if ((rc = sm_nlm_denoise_u8_batch_device(ctx, (const uint8_t*)ctx->rm_src.p, 1, 0, H, W, src_stride, h,
+                                             template_window, search_window, (uint8_t*)ctx->rm_gray.p)) != SM_OK)
+        return rc;
+    {
+        StageTimer t_(ctx, ctx->stream, SM_STAGE_D2H, 1);
+        HIP_TRY(ctx, hipMemcpyAsync(dst, ctx->rm_gray.p, npx, hipMemcpyDeviceToHost, ctx->stream));
     }
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return SM_OK;
