@@ -264,6 +264,71 @@ int sm_nlm_denoise_u8_batch_device(sm_ctx* ctx, const uint8_t* d_src, int nimg, 
  * to query n.  Needs no context and no device. */
 int sm_nlm_weight_table(float h, int template_window, int search_window, int32_t* tab, int* n, int* fpm, int* shift);
 
+/* ---- point clouds: the tail of the reference's scripts
+ * (disparity_calculation.py:302-320, disparity_test.py:230-265, try_try.py:90-96,
+ * mapTo3D_mc_cnn.py:124 ff.): reprojectImageTo3D, cvtColor(BGR2RGB), a disparity-range mask,
+ * points[mask] / colors[mask], and the rows io_functions.write_ply writes (io_functions.py:28-44).
+ *
+ * Mask: lo < d < hi, strict; either bound may be absent.  SM_CLOUD_LO_MIN takes lo from the map
+ * itself, one minimum per image (try_try.py:92; a NaN-free map).  A NaN
+ * disparity passes no bound.  For a float32 map a bound is rounded to float32 before it is
+ * compared, as numpy >= 2 does with a Python scalar; an int16 map compares as the numbers they
+ * are.  A NaN bound is SM_E_ARG.  zero_nonfinite replaces every NaN or +-inf COMPONENT by 0
+ * (disparity_calculation.py:316-317).  handle_missing is reprojectImageTo3D's. */
+#define SM_CLOUD_LO_NONE 0
+#define SM_CLOUD_LO_VALUE 1
+#define SM_CLOUD_LO_MIN 2
+typedef struct sm_cloud_params {
+    double lo, hi;
+    int lo_mode; /* SM_CLOUD_LO_* */
+    int has_hi;
+    int zero_nonfinite;
+    int handle_missing;
+} sm_cloud_params;
+
+/* Sizes: every output buffer comes with its capacity.  Nothing is ever written past a capacity;
+ * the needed size is always reported, and the caller compares.  The host forms return SM_E_ARG
+ * (with the size reported, nothing copied out) when the capacity is too small; the device forms
+ * are asynchronous and report the size in device memory only (rows or bytes that do not fit are
+ * left out).  Capacity 0 with NULL output buffers is the size query.
+ *
+ * Extraction.  For nimg maps [H][W] (disp_type as sm_reproject_image_to_3d: int16 or float32,
+ * densely packed) and their BGR uint8 images (image i at d_bgr + i*bgr_img_stride_bytes, rows
+ * bgr_stride bytes apart, >= 3*W): the pixels that pass the mask, compacted in row-major order,
+ * image i's rows after image i-1's: verts float32 [N][3], bit for bit the pixels of
+ * sm_reproject_image_to_3d, and colors uint8 [N][3] as RGB.  d_counts (nullable): int64 [nimg],
+ * the rows of every image.  H*W <= 2^30, nimg <= 65535. */
+int sm_cloud_extract_batch_device(sm_ctx* ctx, const void* d_disp, int disp_type, const uint8_t* d_bgr,
+                                  size_t bgr_img_stride_bytes, int bgr_stride, int nimg, int H, int W, const double* Q,
+                                  const sm_cloud_params* p, size_t capacity_rows, float* d_verts, uint8_t* d_colors,
+                                  int64_t* d_counts);
+/* One map on host pointers; *count is always set.  Synchronous. */
+int sm_cloud_extract(sm_ctx* ctx, const void* disp, int disp_type, const uint8_t* bgr, int bgr_stride, int H, int W,
+                     const double* Q, const sm_cloud_params* p, size_t capacity_rows, float* verts, uint8_t* colors,
+                     int64_t* count);
+
+/* The PLY body: row i is '%f %f %f %d %d %d ' of (verts[i], colors[i]) and a newline, byte for
+ * byte what Python's formatter (np.savetxt) gives for every float32 bit pattern; a row is at most
+ * 157 bytes.  d_nbytes (nullable unless d_out is NULL): the body's size.  Asynchronous. */
+int sm_ply_format_device(sm_ctx* ctx, const float* d_verts, const uint8_t* d_colors, size_t n, size_t capacity_bytes,
+                         char* d_out, uint64_t* d_nbytes);
+/* The same rows by the same code on the CPU.  Needs no context and no device.  SM_E_ARG with
+ * *nbytes set and nothing written when capacity_bytes is too small. */
+int sm_ply_format_host(const float* verts, const uint8_t* colors, size_t n, size_t capacity_bytes, char* out,
+                       uint64_t* nbytes);
+
+/* Maps to PLY bytes: extraction and formatting back to back on the ctx stream, the vertices kept
+ * in the context's device buffers.  Arguments as the two calls above. */
+int sm_cloud_ply_batch_device(sm_ctx* ctx, const void* d_disp, int disp_type, const uint8_t* d_bgr,
+                              size_t bgr_img_stride_bytes, int bgr_stride, int nimg, int H, int W, const double* Q,
+                              const sm_cloud_params* p, size_t capacity_bytes, char* d_out, int64_t* d_counts,
+                              uint64_t* d_nbytes);
+/* One map on host pointers to the body in host memory; *count and *nbytes are always set.
+ * Synchronous. */
+int sm_cloud_ply(sm_ctx* ctx, const void* disp, int disp_type, const uint8_t* bgr, int bgr_stride, int H, int W,
+                 const double* Q, const sm_cloud_params* p, size_t capacity_bytes, char* out, int64_t* count,
+                 uint64_t* nbytes);
+
 /* ---- StereoBM (the reference's method="BM" branch,
  * stereo_vision/stereo_vision.py:164-166: cv2.StereoBM_create(numDisparities,
  * blockSize)).  Fields follow cv::StereoBM's setters. */
@@ -467,6 +532,9 @@ int sm_set_debug_flags(sm_ctx* ctx, int flags);
  *   SM_TUNE_LR_STAGGER sm_compute_disparity*: 0 automatic / 1 the left matcher starts on a
  *                      second stream once the right one's down sweep is done (overlapping its
  *                      patch passes and WTA); -1 the matchers strictly one after the other.
+ *   SM_TUNE_PLY_STAGE  the PLY formatter's write pass: 0 automatic / 1 a block's rows staged in
+ *                      LDS and streamed out in 16-byte stores, -1 every row straight to global
+ *                      memory (the same bytes; DESIGN.md §4.9 has the measurement).
  * Returns SM_E_ARG for an unknown key or value. */
 #define SM_TUNE_EW_LANES 1
 #define SM_TUNE_SWEEP_NCW 2
@@ -481,6 +549,7 @@ int sm_set_debug_flags(sm_ctx* ctx, int flags);
 #define SM_TUNE_COST_WGS 11
 #define SM_TUNE_LR_STAGGER 12
 #define SM_TUNE_SWEEP_XCD 13
+#define SM_TUNE_PLY_STAGE 14
 int sm_set_tuning(sm_ctx* ctx, int key, int value);
 
 /* Last error text of ctx (or of the calling thread when ctx == NULL). */

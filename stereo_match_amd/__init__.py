@@ -11,6 +11,8 @@ Public surface (mirrors the reference / OpenCV names the reference uses):
   ``disparity_calculation.py:131-210,286-287``
 * :func:`fastNlMeansDenoising` — the denoiser in front of the matcher in the test flow,
   ``disparity_test.py:94-95``
+* :func:`extract_point_cloud`, :func:`format_ply`, :func:`write_point_cloud` — the masked point
+  cloud and its ASCII PLY file, the tail of every script (``disparity_calculation.py:302-320``)
 
 All compute runs in ``libstereo_match_amd.so`` (HIP, gfx950) through the
 C-ABI in ``include/stereo_match_amd.h``; there is no CPU fallback.
@@ -25,6 +27,7 @@ from .reproject import project_points_3D, reprojectImageTo3D, write_ply
 from .rectify import (CALIB_ZERO_DISPARITY, COLOR_BGR2GRAY, CV_32FC1, INTER_LINEAR, StereoRectifier, cvtColor,
                       initUndistortRectifyMap, rectify_opencv, remap, stereoRectify)
 from .denoise import fastNlMeansDenoising
+from .pointcloud import extract_point_cloud, format_ply, write_point_cloud
 
 __all__ = [
     "compute_disparity", "matcher_from_settings", "StereoSGBM", "StereoSGBM_create", "createRightMatcher",
@@ -33,5 +36,6 @@ __all__ = [
     "project_points_3D", "write_ply", "StereoBM", "StereoBM_create",
     "stereoRectify", "initUndistortRectifyMap", "remap", "cvtColor", "rectify_opencv", "StereoRectifier",
     "CALIB_ZERO_DISPARITY", "CV_32FC1", "INTER_LINEAR", "COLOR_BGR2GRAY", "fastNlMeansDenoising",
+    "extract_point_cloud", "format_ply", "write_point_cloud",
 ]
 __version__ = "0.1.0"

@@ -65,6 +65,15 @@ class SmRectifyCam(ctypes.Structure):
     _fields_ = [("K", ctypes.c_double * 9), ("dist", ctypes.c_double * 5), ("iR", ctypes.c_double * 9)]
 
 
+class SmCloudParams(ctypes.Structure):
+    """Mirror of ``struct sm_cloud_params`` (point-cloud mask and options)."""
+    _fields_ = [("lo", ctypes.c_double), ("hi", ctypes.c_double), ("lo_mode", ctypes.c_int),
+                ("has_hi", ctypes.c_int), ("zero_nonfinite", ctypes.c_int), ("handle_missing", ctypes.c_int)]
+
+
+SM_CLOUD_LO_NONE, SM_CLOUD_LO_VALUE, SM_CLOUD_LO_MIN = 0, 1, 2
+PLY_MAX_ROW = 157  # bytes of the longest row '%f %f %f %d %d %d ' + newline
+
 ABI_VERSION = 3  # include/stereo_match_amd.h SM_ABI_VERSION this binding is written against
 
 _c = ctypes
@@ -130,6 +139,23 @@ _SIGS = {
                                                   _c.c_int, _c.c_float, _c.c_int, _c.c_int, _c.c_void_p]),
     "sm_nlm_weight_table": (_c.c_int, [_c.c_float, _c.c_int, _c.c_int, _c.c_void_p, _c.POINTER(_c.c_int),
                                        _c.POINTER(_c.c_int), _c.POINTER(_c.c_int)]),
+    "sm_cloud_extract_batch_device": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_size_t, _c.c_int,
+                                                 _c.c_int, _c.c_int, _c.c_int, _c.c_void_p,
+                                                 _c.POINTER(SmCloudParams), _c.c_size_t, _c.c_void_p, _c.c_void_p,
+                                                 _c.c_void_p]),
+    "sm_cloud_extract": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int,
+                                    _c.c_void_p, _c.POINTER(SmCloudParams), _c.c_size_t, _c.c_void_p, _c.c_void_p,
+                                    _c.POINTER(_c.c_int64)]),
+    "sm_ply_format_device": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_size_t, _c.c_void_p,
+                                        _c.c_void_p]),
+    "sm_ply_format_host": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_size_t, _c.c_void_p,
+                                      _c.POINTER(_c.c_uint64)]),
+    "sm_cloud_ply_batch_device": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_size_t, _c.c_int,
+                                             _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.POINTER(SmCloudParams),
+                                             _c.c_size_t, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "sm_cloud_ply": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int,
+                                _c.c_void_p, _c.POINTER(SmCloudParams), _c.c_size_t, _c.c_void_p,
+                                _c.POINTER(_c.c_int64), _c.POINTER(_c.c_uint64)]),
     "sm_bm_default_params": (_c.c_int, [_c.c_int, _c.c_int, _c.POINTER(SmBmParams)]),
     "sm_bm_right_matcher_params": (_c.c_int, [_c.POINTER(SmBmParams), _c.POINTER(SmBmParams)]),
     "sm_bm_compute": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int,
@@ -165,6 +191,33 @@ def wls_default_params(left: SmParams) -> SmWlsParams:
     if rc != SM_OK:
         _raise(rc, None)
     return out
+
+
+def ply_format_host(verts: np.ndarray, colors: np.ndarray, capacity: int = None) -> np.ndarray:
+    """sm_ply_format_host: the PLY body of float32 verts [N, 3] and uint8 colors [N, 3] as a uint8
+    array, formatted on the CPU by the row function the GPU kernels use.  Needs no context and no
+    device.  ``capacity`` (default: the exact size, asked for first) bounds the output buffer; a
+    body that does not fit is a ValueError and nothing is written."""
+    lib = load()
+    v = np.ascontiguousarray(verts)
+    c = np.ascontiguousarray(colors)
+    if v.dtype != np.float32 or c.dtype != np.uint8 or v.ndim != 2 or v.shape[1] != 3 or c.shape != v.shape:
+        raise ValueError("ply_format_host: float32 verts [N, 3] and uint8 colors [N, 3]")
+    n = v.shape[0]
+    nb = ctypes.c_uint64()
+    if capacity is None:
+        rc = lib.sm_ply_format_host(v.ctypes.data, c.ctypes.data, n, 0, None, ctypes.byref(nb))
+        if nb.value == 0:
+            if rc != SM_OK:
+                _raise(rc, None)
+            return np.empty(0, np.uint8)
+        capacity = nb.value
+    out = np.empty(int(capacity), np.uint8)
+    rc = lib.sm_ply_format_host(v.ctypes.data, c.ctypes.data, n, out.size, out.ctypes.data if out.size else None,
+                                ctypes.byref(nb))
+    if rc != SM_OK:
+        _raise(rc, None)
+    return out[:nb.value]
 
 
 def volume_scale(scale) -> float:
@@ -503,6 +556,55 @@ class Engine:
         self._check(self._lib.sm_bgr2gray_u8_batch_device(self.ctx, ctypes.c_void_p(d_src), nimg, img_stride, H, W,
                                                           src_stride, ctypes.c_void_p(d_gray)))
 
+    # -- point clouds ------------------------------------------------------
+    def cloud_extract(self, disp: np.ndarray, kind: int, bgr: np.ndarray, Q: np.ndarray, prm: "SmCloudParams"):
+        """sm_cloud_extract on a C-contiguous [H, W] map and a uint8 [H, W, 3] image whose pixels
+        are contiguous (any row stride): (verts float32 [N, 3], colors uint8 [N, 3] RGB)."""
+        H, W = disp.shape
+        Qd = np.ascontiguousarray(np.asarray(Q, np.float64).reshape(16))
+        verts = np.empty((H * W, 3), np.float32)
+        colors = np.empty((H * W, 3), np.uint8)
+        n = ctypes.c_int64()
+        self._check(self._lib.sm_cloud_extract(self.ctx, disp.ctypes.data, kind, bgr.ctypes.data, bgr.strides[0], H, W,
+                                               Qd.ctypes.data, ctypes.byref(prm), H * W, verts.ctypes.data,
+                                               colors.ctypes.data, ctypes.byref(n)))
+        return verts[:n.value].copy(), colors[:n.value].copy()
+
+    def cloud_extract_batch_device(self, d_disp: int, kind: int, d_bgr: int, img_stride: int, bgr_stride: int,
+                                   nimg: int, H: int, W: int, Q: np.ndarray, prm: "SmCloudParams", capacity_rows: int,
+                                   d_verts: int, d_colors: int, d_counts: int):
+        Qd = np.ascontiguousarray(np.asarray(Q, np.float64).reshape(16))
+        self._check(self._lib.sm_cloud_extract_batch_device(
+            self.ctx, ctypes.c_void_p(d_disp), kind, ctypes.c_void_p(d_bgr), img_stride, bgr_stride, nimg, H, W,
+            Qd.ctypes.data, ctypes.byref(prm), capacity_rows, ctypes.c_void_p(d_verts) if d_verts else None,
+            ctypes.c_void_p(d_colors) if d_colors else None, ctypes.c_void_p(d_counts) if d_counts else None))
+
+    def ply_format_device(self, d_verts: int, d_colors: int, n: int, capacity_bytes: int, d_out: int, d_nbytes: int):
+        self._check(self._lib.sm_ply_format_device(
+            self.ctx, ctypes.c_void_p(d_verts) if d_verts else None, ctypes.c_void_p(d_colors) if d_colors else None, n,
+            capacity_bytes, ctypes.c_void_p(d_out) if d_out else None, ctypes.c_void_p(d_nbytes) if d_nbytes else None))
+
+    def cloud_ply_batch_device(self, d_disp: int, kind: int, d_bgr: int, img_stride: int, bgr_stride: int, nimg: int,
+                               H: int, W: int, Q: np.ndarray, prm: "SmCloudParams", capacity_bytes: int, d_out: int,
+                               d_counts: int, d_nbytes: int):
+        Qd = np.ascontiguousarray(np.asarray(Q, np.float64).reshape(16))
+        self._check(self._lib.sm_cloud_ply_batch_device(
+            self.ctx, ctypes.c_void_p(d_disp), kind, ctypes.c_void_p(d_bgr), img_stride, bgr_stride, nimg, H, W,
+            Qd.ctypes.data, ctypes.byref(prm), capacity_bytes, ctypes.c_void_p(d_out) if d_out else None,
+            ctypes.c_void_p(d_counts) if d_counts else None, ctypes.c_void_p(d_nbytes) if d_nbytes else None))
+
+    def cloud_ply(self, disp: np.ndarray, kind: int, bgr: np.ndarray, Q: np.ndarray, prm: "SmCloudParams"):
+        """sm_cloud_ply: (PLY body as a uint8 array, N).  The buffer handed to the library is sized
+        for the longest possible rows; only the pages the body reaches are ever touched."""
+        H, W = disp.shape
+        Qd = np.ascontiguousarray(np.asarray(Q, np.float64).reshape(16))
+        out = np.empty(H * W * PLY_MAX_ROW, np.uint8)
+        n, nb = ctypes.c_int64(), ctypes.c_uint64()
+        self._check(self._lib.sm_cloud_ply(self.ctx, disp.ctypes.data, kind, bgr.ctypes.data, bgr.strides[0], H, W,
+                                           Qd.ctypes.data, ctypes.byref(prm), out.size, out.ctypes.data,
+                                           ctypes.byref(n), ctypes.byref(nb)))
+        return out[:nb.value], n.value
+
     # -- fastNlMeansDenoising -------------------------------------------------------------
     def nlm_denoise(self, src: np.ndarray, h: float, template_window: int, search_window: int,
                     dst: np.ndarray = None) -> np.ndarray:
@@ -625,6 +727,7 @@ class Engine:
     TUNE_EW_LANES, TUNE_SWEEP_NCW, TUNE_EW_WAVES, TUNE_EW_PRIO, TUNE_EW_WARMUP, TUNE_SWEEP_LINES = 1, 2, 3, 4, 5, 6
     TUNE_EW_GUESS = 7
     TUNE_BANDS, TUNE_BAND_WARMUP, TUNE_BAND_GUESS, TUNE_COST_WGS, TUNE_LR_STAGGER, TUNE_SWEEP_XCD = 8, 9, 10, 11, 12, 13
+    TUNE_PLY_STAGE = 14
 
     def set_tuning(self, key: int, value: int):
         """Launch-shape knob (include/stereo_match_amd.h sm_set_tuning); 0 = automatic."""

@@ -24,6 +24,26 @@ struct ReprojArgs {
 __device__ inline float disp_value(const int16_t* p, size_t i) { return (float)p[i]; }
 __device__ inline float disp_value(const float* p, size_t i) { return p[i]; }
 
+// one pixel: the arithmetic above.  Shared by k_reproject and the point-cloud extraction
+// (sm_cloud.hpp), so that a compacted vertex is the full image's pixel bit for bit.
+__device__ inline void reproject_point(const double* Q, int x, int y, double d, int handle_missing, double md,
+                                       float* o)
+{
+#pragma clang fp contract(off)
+    const double qx = Q[1] * y + Q[3] + Q[0] * x;
+    const double qy = Q[5] * y + Q[7] + Q[4] * x;
+    const double qz = Q[9] * y + Q[11] + Q[8] * x;
+    const double qw = Q[13] * y + Q[15] + Q[12] * x;
+    const double iW = 1.0 / (qw + Q[14] * d);
+    const double X = (qx + Q[2] * d) * iW;
+    const double Y = (qy + Q[6] * d) * iW;
+    double Z = (qz + Q[10] * d) * iW;
+    if (handle_missing && fabs(d - md) <= 1.1920928955078125e-07) Z = 10000.0;  // FLT_EPSILON, bigZ
+    o[0] = (float)X;
+    o[1] = (float)Y;
+    o[2] = (float)Z;
+}
+
 template <typename T>
 __global__ void __launch_bounds__(256) k_reproject(ReprojArgs a)
 {
@@ -33,23 +53,8 @@ __global__ void __launch_bounds__(256) k_reproject(ReprojArgs a)
     const size_t npx = (size_t)a.H * a.W;
     const size_t i = img * npx + (size_t)y * a.W + x;
     const double d = (double)disp_value(reinterpret_cast<const T*>(a.disp), i);
-    const double* Q = a.Q;
-    const double qx = Q[1] * y + Q[3] + Q[0] * x;
-    const double qy = Q[5] * y + Q[7] + Q[4] * x;
-    const double qz = Q[9] * y + Q[11] + Q[8] * x;
-    const double qw = Q[13] * y + Q[15] + Q[12] * x;
-    const double iW = 1.0 / (qw + Q[14] * d);
-    const double X = (qx + Q[2] * d) * iW;
-    const double Y = (qy + Q[6] * d) * iW;
-    double Z = (qz + Q[10] * d) * iW;
-    if (a.handle_missing) {
-        const double md = (double)a.min_disp[img];
-        if (fabs(d - md) <= 1.1920928955078125e-07) Z = 10000.0;  // FLT_EPSILON, bigZ
-    }
-    float* o = a.xyz + 3 * i;
-    o[0] = (float)X;
-    o[1] = (float)Y;
-    o[2] = (float)Z;
+    const double md = a.handle_missing ? (double)a.min_disp[img] : 0.0;
+    reproject_point(a.Q, x, y, d, a.handle_missing, md, a.xyz + 3 * i);
 }
 
 // per-image minimum (handleMissingValues): order-preserving int key of float
