@@ -749,6 +749,7 @@ struct SweepJob {
     size_t st_pair = 0;     // bytes
     int ewarm = 0;          // MODE 3: warmup columns of the E/W segments
     int ewguess = 0;        // MODE 3: 1 = a deliberately wrong start state (tests)
+    int part_il = 0;        // MODES 3 / 4: the partial's lane slices interleaved (SweepArgs::part_il)
     // MODE 3 row bands (nband > 1: the wide instance)
     int nband = 1, band_h = 0, vwarm = 0, vguess = 0;
     uint8_t* vst = nullptr;
@@ -933,6 +934,7 @@ int sweep_pass(sm_ctx* ctx, const Norm& n, const Geo& g, const SweepJob& j, int 
         a.st_pair = j.st_pair;
         a.ewarm = j.ewarm;
         a.ewguess = j.ewguess;
+        a.part_il = j.part_il;
         a.nband = nb;
         a.band_h = j.band_h;
         a.vwarm = j.vwarm;
@@ -1208,6 +1210,11 @@ int run_lines(sm_ctx* ctx, const Norm& n, const Geo& g, BufSet& bs, hipStream_t 
     j.st = (uint8_t*)bs.st.p;
     j.ewarm = ew_warmup(ctx, n);
     j.ewguess = ctx->tune_ew_guess;
+    // 8 paths on u8 costs: the partial goes from MODE 3 through k_ew_patch to MODE 4 only, so it keeps
+    // the sweeps' interleaved lane slices where the patch pass's lines (16 lanes where D % 32 == 0,
+    // else 8) are the sweeps' (not D = 256: the wide and narrow sweeps differ there)
+    j.part_il = SWEEP_IL && n.ndirs == 8 && et == 1 && n.D != 256 && f.si.dpl % 2 == 0 &&
+                f.si.dpl == (n.D % 32 == 0 ? n.D / 16 : n.D / 8) ? 1 : 0;
     // one or two pairs (row bands): the patch passes' longest walks are the call's critical
     // path, so the u16 segments warm up longer (settings.ini D = 160, one pair: 24 -> 54 columns,
     // E/W repairs 551 -> 26 per matcher, device time per call 1114 -> 1058 us)
@@ -1252,6 +1259,7 @@ int run_lines(sm_ctx* ctx, const Norm& n, const Geo& g, BufSet& bs, hipStream_t 
         // u16 costs where no partial cell can saturate: atomic corrections, E and W side by side
         // (sm_ew.hpp ATOM; sgbm5 8 pairs: patch 17.6 -> 15.2 us per pair; census8: 6.9 -> 7.5)
         pa.atom = EW_PATCH_ATOM && et == 2 && 5 * path_max(n) < 65536 ? 1 : 0;
+        pa.part_il = j.part_il;
         auto ew_patch = [&](hipStream_t st) -> int {
             const hipError_t e = smk::ew_patch_launch(n.D, (int)et, pa, G, st);
             if (e == hipErrorInvalidValue) return fail(ctx, SM_E_UNSUPPORTED, "E/W patch: numDisparities %d not built", n.D);

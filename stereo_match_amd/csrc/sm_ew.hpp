@@ -191,6 +191,10 @@ __global__ void __launch_bounds__(256) k_ew_patch(EwPatchArgs a)
     const rsrc_t rs = make_rsrc(a.st + pair * a.st_pair, a.st_pair);
     const uint32_t P1p = (uint32_t)a.P1 * 0x10001u, P2p = (uint32_t)a.P2 * 0x10001u;
     const uint32_t eL = g == 0 ? EDGE : 0u, eR = g == VL - 1 ? EDGE : 0u;
+    // the partial's lane slices (this kernel's lines are the sweeps') interleaved, sm_pk.hpp pk_disp:
+    // the walks convert a slice at its load and its store (NP v_perm_b32 each, repaired columns
+    // only); the carried walks then stay on these lines (the 64-lane lines cut a slice differently)
+    const bool pil = !ATOM && a.part_il != 0;  // (wave-uniform)
     auto soff = [&](int k, int dir, int which) -> uint32_t {
         return (((((uint32_t)y * (uint32_t)nwg + (uint32_t)k) * 2u + (uint32_t)dir) * 2u + (uint32_t)which) *
                     (uint32_t)D + (uint32_t)(g * DPL)) * (uint32_t)sizeof(CT);
@@ -261,6 +265,12 @@ __global__ void __launch_bounds__(256) k_ew_patch(EwPatchArgs a)
                 unpack_ct_pk<CT, DPL>(cc[u], C2[0]);
 #pragma unroll
                 for (int q = 0; q < NP; q++) pv_[q] = ATOM ? 0u : pb[u].w[q];
+                if (pil) {  // the lane's slice of an interleaved partial -> d-contiguous words
+                    uint32_t t[NP];
+                    pk_to_plain<NP, true>(pv_, t);
+#pragma unroll
+                    for (int q = 0; q < NP; q++) pv_[q] = t[q];
+                }
 #pragma unroll
                 for (int q = 0; q < NP; q++) C2[1][q] = C2[0][q];
                 sweep_step2n<VL, NP, H16, 2>(Lq, mq, C2, P1p, P2p, eL, eR, Ln, mn);
@@ -285,6 +295,12 @@ __global__ void __launch_bounds__(256) k_ew_patch(EwPatchArgs a)
                     } else {  // census: every sum < 2^11, the u16 wrap is exact
                         P[q] = pk_add(pk_sub(pv_[q], Ln[0][q]), Ln[1][q]);
                     }
+                }
+                if (pil) {  // and back
+                    uint32_t t[NP];
+                    pk_from_plain<NP, true>(P, t);
+#pragma unroll
+                    for (int q = 0; q < NP; q++) P[q] = t[q];
                 }
                 if constexpr (!ATOM) bstore_n<uint32_t, NP>(rp, cell(c) * 2u, P);
 #pragma unroll
@@ -480,7 +496,7 @@ __global__ void __launch_bounds__(256) k_ew_patch(EwPatchArgs a)
             if (lane == 0) openm[wave][ch] = open;
             if (open && first_open == nwg) first_open = i0 + __builtin_ctzll(open);
         }
-        if (first_open < nwg && !EW_PATCH_NO_CARRY && D % 128 == 0 && EW_PATCH_B64) {
+        if (first_open < nwg && !EW_PATCH_NO_CARRY && D % 128 == 0 && EW_PATCH_B64 && !pil) {
             // ---- phase B on 64-lane lines (the same walk, the whole wave)
             order_partial();  // the other lanes' partial and c_k stores
             bool carry = false;

@@ -92,6 +92,68 @@ __device__ __forceinline__ uint32_t pk_adds(uint32_t a, uint32_t b)
     return pkw(__builtin_elementwise_add_sat(pkv(a), pkv(b)));
 }
 
+// ---- layout of a lane's 2 NP disparities in its NP packed words.  Word order is 2 * word + half.
+//   plain (IL = false): word k = (d_2k, d_2k+1), the order of every volume in memory;
+//   interleaved (IL = true): word k = (d_k, d_k+NP).  The d - 1 / d + 1 neighbours of both
+//   halves of word k are then words k - 1 / k + 1 as a whole: the recurrence needs a funnel
+//   shift only for word 0's lower and word NP - 1's upper neighbours, and the halves of a
+//   word are NP apart, so a word's half swap never pairs neighbours.
+// pk_disp: lane-local disparity of (word k, half h); pk_slot: its inverse, lane-local
+// disparity r -> position 2 * word + half (the u16 index inside the lane's slice of a row kept
+// in word order)
+template <int NP, bool IL>
+__device__ __forceinline__ constexpr int pk_disp(int k, int h)
+{
+    return IL ? k + h * NP : 2 * k + h;
+}
+template <int NP, bool IL>
+__device__ __forceinline__ constexpr int pk_slot(int r)
+{
+    return IL ? (r < NP ? 2 * r : 2 * (r - NP) + 1) : r;
+}
+// one word from a half of lo_src (low result half) and a half of hi_src (v_perm_b32)
+__device__ __forceinline__ uint32_t pk_halves(uint32_t lo_src, int lo_half, uint32_t hi_src, int hi_half)
+{
+    return __builtin_amdgcn_perm(hi_src, lo_src, ((hi_half ? 0x0706u : 0x0504u) << 16) | (lo_half ? 0x0302u : 0x0100u));
+}
+// a lane's words between its layout and the plain (d-contiguous) order of the volumes in
+// memory: NP v_perm_b32 each way for IL, nothing otherwise
+template <int NP, bool IL>
+__device__ __forceinline__ void pk_to_plain(const uint32_t (&w)[NP], uint32_t (&o)[NP])
+{
+#pragma unroll
+    for (int j = 0; j < NP; j++) {
+        if constexpr (IL) {
+            const int s0 = pk_slot<NP, true>(2 * j), s1 = pk_slot<NP, true>(2 * j + 1);
+            o[j] = pk_halves(w[s0 >> 1], s0 & 1, w[s1 >> 1], s1 & 1);
+        } else {
+            o[j] = w[j];
+        }
+    }
+}
+template <int NP, bool IL>
+__device__ __forceinline__ void pk_from_plain(const uint32_t (&p)[NP], uint32_t (&w)[NP])
+{
+#pragma unroll
+    for (int k = 0; k < NP; k++) {
+        if constexpr (IL) w[k] = pk_halves(p[k >> 1], k & 1, p[(k + NP) >> 1], (k + NP) & 1);
+        else w[k] = p[k];
+    }
+}
+// min(w, w with its halves swapped): a lane's own minimum, replicated in both halves (the
+// swap folds into the packed minimum's op_sel: one instruction)
+template <bool H16>
+__device__ __forceinline__ uint32_t pk_min_halves(uint32_t w)
+{
+    if constexpr (H16) {
+        const auto v = __builtin_bit_cast(_Float16 __attribute__((ext_vector_type(2))), w);
+        return __builtin_bit_cast(uint32_t, __builtin_elementwise_minimum(v, __builtin_shufflevector(v, v, 1, 0)));
+    } else {
+        const pk16 v = pkv(w);
+        return pkw(__builtin_elementwise_min(v, __builtin_shufflevector(v, v, 1, 0)));
+    }
+}
+
 // min(s + u * 0xFFFF, 0xFFFF) per u16 half (v_pk_mad_u16 with clamp; with the product
 // truncated to 16 bits it is still >= 0xFFFD for u in 1..3): the uniqueness test's window
 // entries (u = 3 - t > 0) pushed above every sum, the others (u = 0) unchanged, in one
@@ -173,6 +235,11 @@ __device__ __forceinline__ uint32_t sweep_step_h16(const uint32_t (&Lp)[NP], uin
     return group_min<VL>(::min(mn & 0xFFFFu, mn >> 16));
 }
 
+template <int VL, int NP, bool H16, int ND, bool DS = false, bool IL = false>
+__device__ __forceinline__ void sweep_step2n(const uint32_t (&Lp)[ND][NP], const uint32_t (&mmp)[ND],
+                                             const uint32_t (&C)[ND][NP], uint32_t P1p, uint32_t P2p, uint32_t eL,
+                                             uint32_t eR, uint32_t (&Ln)[ND][NP], uint32_t (&mn)[ND]);
+
 // The fused sweeps' form of the step (u16 or, for census, the f16 form):
 //  * the row minimum travels replicated in both halves (m | m << 16): a lane's own
 //    minimum is min(w, swap(w)) and the cross-lane steps are plain u32 minima (on
@@ -181,11 +248,26 @@ __device__ __forceinline__ uint32_t sweep_step_h16(const uint32_t (&Lp)[NP], uin
 //  * 16-lane lines take the d - 1 / d + 1 neighbours across lanes with zero-filling DPP
 //    moves OR'ed with the per-lane edge constants eL / eR (EDGE on the line's first /
 //    last lane, 0 elsewhere), which the compiler fuses into one v_or_b32_dpp each.
-template <int VL, int NP, bool H16, bool DS = false>
+// IL: the words in the interleaved layout (pk_disp): Lp, C and Ln are word k = (d_k, d_k+NP);
+// the same operations per disparity in the same order, hence the same values, with two funnel
+// shifts per step instead of NP + 1 and the half swap of the minimum inside the packed minimum.
+template <int VL, int NP, bool H16, bool DS = false, bool IL = false>
 __device__ __forceinline__ uint32_t sweep_step2(const uint32_t (&Lp)[NP], uint32_t mmp, const uint32_t (&C)[NP],
                                                 uint32_t P1p, uint32_t P2p, uint32_t eL, uint32_t eR,
                                                 uint32_t (&Ln)[NP])
 {
+    if constexpr (IL) {  // one recurrence of the stage-wise form
+        uint32_t Lp1[1][NP], m1[1] = {mmp}, C1[1][NP], Ln1[1][NP], mn1[1];
+#pragma unroll
+        for (int k = 0; k < NP; k++) {
+            Lp1[0][k] = Lp[k];
+            C1[0][k] = C[k];
+        }
+        sweep_step2n<VL, NP, H16, 1, DS, true>(Lp1, m1, C1, P1p, P2p, eL, eR, Ln1, mn1);
+#pragma unroll
+        for (int k = 0; k < NP; k++) Ln[k] = Ln1[0][k];
+        return mn1[0];
+    }
     static_assert(!DS || H16, "deferred subtraction (sweep_step2n): census f16 form only");
     constexpr uint32_t EDGE = H16 ? 0x7BFF7BFFu : (kBig | (kBig << 16));
     uint32_t lm, lq;
@@ -280,7 +362,10 @@ __device__ __forceinline__ void group_min_n(uint32_t (&v)[ND])
 // R_next - minR of that state).  The caller subtracts the input minima once per sum of paths
 // instead of once per word and path, and renormalises the state (R - minR) often enough that
 // every value stays below the f16 form's 2^11 (sm_sweep.hpp SWEEP_DS).
-template <int VL, int NP, bool H16, int ND, bool DS = false>
+// IL (interleaved layout, see sweep_step2): the neighbour words of word k are words k - 1 and
+// k + 1 themselves; a1 is word 0's lower neighbour pair (the previous lane's last disparity, own
+// d_NP-1), a2 word NP - 1's upper pair (own d_NP, the next lane's first disparity).
+template <int VL, int NP, bool H16, int ND, bool DS, bool IL>
 __device__ __forceinline__ void sweep_step2n(const uint32_t (&Lp)[ND][NP], const uint32_t (&mmp)[ND],
                                              const uint32_t (&C)[ND][NP], uint32_t P1p, uint32_t P2p, uint32_t eL,
                                              uint32_t eR, uint32_t (&Ln)[ND][NP], uint32_t (&mn)[ND])
@@ -309,25 +394,39 @@ __device__ __forceinline__ void sweep_step2n(const uint32_t (&Lp)[ND][NP], const
 #pragma unroll
     for (int n = 0; n < ND; n++) {
         dl[n] = H16 ? h2add(mmp[n], P2p) : pk_add(mmp[n], P2p);
-        a1[n] = __builtin_amdgcn_alignbit(Lp[n][0], lm[n], 16);
+        a1[n] = __builtin_amdgcn_alignbit(Lp[n][IL ? NP - 1 : 0], lm[n], 16);
     }
     // the words of one recurrence are independent too (a word's d-1 / d+1 neighbours come
     // from the previous step's L), so every stage runs over all ND x NP words before the next
     uint32_t v[ND][NP];
+    if constexpr (IL) {
+        uint32_t a2[ND];
 #pragma unroll
-    for (int k = 0; k < NP; k++) {
+        for (int n = 0; n < ND; n++) a2[n] = __builtin_amdgcn_alignbit(lq[n], Lp[n][0], 16);
 #pragma unroll
-        for (int n = 0; n < ND; n++)
-            v[n][k] = __builtin_amdgcn_alignbit(k + 1 < NP ? Lp[n][k + 1] : lq[n], Lp[n][k], 16);
-    }
-    // v[n][k] now holds the (d+1, d+2) neighbours of word k; (d-1, d) = a1 for k = 0, else
-    // v[n][k-1]
+        for (int k = 0; k < NP; k++) {
 #pragma unroll
-    for (int k = NP - 1; k >= 0; k--) {
+            for (int n = 0; n < ND; n++) {
+                const uint32_t lo = k == 0 ? a1[n] : Lp[n][k - 1], hi = k == NP - 1 ? a2[n] : Lp[n][k + 1];
+                v[n][k] = H16 ? h2min(lo, hi) : pk_min(lo, hi);
+            }
+        }
+    } else {
 #pragma unroll
-        for (int n = 0; n < ND; n++) {
-            const uint32_t lo = k == 0 ? a1[n] : v[n][k - 1];
-            v[n][k] = H16 ? h2min(lo, v[n][k]) : pk_min(lo, v[n][k]);
+        for (int k = 0; k < NP; k++) {
+#pragma unroll
+            for (int n = 0; n < ND; n++)
+                v[n][k] = __builtin_amdgcn_alignbit(k + 1 < NP ? Lp[n][k + 1] : lq[n], Lp[n][k], 16);
+        }
+        // v[n][k] now holds the (d+1, d+2) neighbours of word k; (d-1, d) = a1 for k = 0, else
+        // v[n][k-1]
+#pragma unroll
+        for (int k = NP - 1; k >= 0; k--) {
+#pragma unroll
+            for (int n = 0; n < ND; n++) {
+                const uint32_t lo = k == 0 ? a1[n] : v[n][k - 1];
+                v[n][k] = H16 ? h2min(lo, v[n][k]) : pk_min(lo, v[n][k]);
+            }
         }
     }
     if constexpr (H16) {
@@ -380,7 +479,8 @@ __device__ __forceinline__ void sweep_step2n(const uint32_t (&Lp)[ND][NP], const
             for (int n = 0; n < ND; n++) mn[n] = k + 1 < NP ? h2min3(mn[n], Ln[n][k], Ln[n][k + 1]) : h2min(mn[n], Ln[n][k]);
         }
 #pragma unroll
-        for (int n = 0; n < ND; n++) mn[n] = h2min(mn[n], __builtin_amdgcn_alignbit(mn[n], mn[n], 16));
+        for (int n = 0; n < ND; n++)
+            mn[n] = IL ? pk_min_halves<true>(mn[n]) : h2min(mn[n], __builtin_amdgcn_alignbit(mn[n], mn[n], 16));
     } else {
 #pragma unroll
         for (int k = 1; k < NP; k++) {
@@ -388,7 +488,8 @@ __device__ __forceinline__ void sweep_step2n(const uint32_t (&Lp)[ND][NP], const
             for (int n = 0; n < ND; n++) mn[n] = pk_min(mn[n], Ln[n][k]);
         }
 #pragma unroll
-        for (int n = 0; n < ND; n++) mn[n] = pk_min(mn[n], __builtin_amdgcn_alignbit(mn[n], mn[n], 16));
+        for (int n = 0; n < ND; n++)
+            mn[n] = IL ? pk_min_halves<false>(mn[n]) : pk_min(mn[n], __builtin_amdgcn_alignbit(mn[n], mn[n], 16));
     }
     group_min_n<VL, ND>(mn);  // replicated halves: u32 minima are exact
 }
@@ -422,6 +523,36 @@ __device__ __forceinline__ void unpack_ct_pk(const RawBytes<DPL * (int)sizeof(CT
         if constexpr (sizeof(CT) == 2) C[k] = r.w[k];
         else C[k] = __builtin_amdgcn_perm(0u, r.w[k >> 1], (k & 1) ? 0x0c030c02u : 0x0c010c00u);
     }
+}
+
+// the same for a lane in layout IL: the bytes in memory are d-contiguous (a cost, E / W or
+// boundary-state slice) either way.  u8: one v_perm_b32 per word as above, word k taking bytes
+// k and k + NP of the slice; u16: the plain words, then pk_from_plain
+template <typename CT, int DPL, bool IL>
+__device__ __forceinline__ void unpack_vol_pk(const RawBytes<DPL * (int)sizeof(CT)>& r, uint32_t (&C)[DPL / 2])
+{
+    constexpr int NP = DPL / 2;
+    if constexpr (!IL) {
+        unpack_ct_pk<CT, DPL>(r, C);
+    } else if constexpr (sizeof(CT) == 2) {
+        uint32_t p[NP];
+        unpack_ct_pk<CT, DPL>(r, p);
+        pk_from_plain<NP, true>(p, C);
+    } else {
+#pragma unroll
+        for (int k = 0; k < NP; k++)
+            C[k] = __builtin_amdgcn_perm(r.w[(k + NP) >> 2], r.w[k >> 2],
+                                         0x0c000c00u | (uint32_t)(k & 3) | ((uint32_t)(4 + ((k + NP) & 3)) << 16));
+    }
+}
+
+// a lane's words in layout IL -> d-contiguous LT bytes at byte offset off
+template <typename LT, int NP, bool IL, int AUX = 0>
+__device__ __forceinline__ void store_vol_pk(rsrc_t r, uint32_t off, const uint32_t (&w)[NP])
+{
+    uint32_t p[NP];
+    pk_to_plain<NP, IL>(w, p);
+    store_pk<LT, NP, AUX>(r, off, p);
 }
 
 }  // namespace smk

@@ -120,6 +120,23 @@ static_assert(62 * SWEEP_DS_RN + 62 + 193 + 192 < 2048, "DS renormalisation inte
 #ifndef SWEEP_LDS_FIRST
 #define SWEEP_LDS_FIRST 1  // a scheduling barrier after the row's LDS reads (see the row loop)
 #endif
+// packed row loops on u8 costs: a lane's words in the interleaved layout (sm_pk.hpp pk_disp),
+// word k = (d_k, d_k+NP): NP - 1 funnel shifts and one half swap fewer per recurrence step.
+// The LDS rows lv, the line ring, srow and the halo snapshots are in word order (k_sweep alone
+// reads them).  What another kernel reads or writes keeps its d-contiguous form: cost and E / W
+// slices (u8: converted inside the one v_perm_b32 per word their unpacking takes anyway), the
+// boundary states st / vst (converted at their rare stores), the records.  The u16 partial is in
+// word order where only MODE 3, k_ew_patch and MODE 4 touch it (SweepArgs::part_il: 8 paths, the
+// patch pass on lines of the sweeps' geometry) and d-contiguous otherwise (MODE 0 for MODE 2 and
+// the hybrid engine, MODE 3 for k_wta and k_band_patch at 5 paths, D = 256): NP v_perm_b32 at its
+// store and at its load.  u16 costs (NP more permutes per cost load, none to fold them into)
+// keep the plain layout.
+// (SWEEP_IL itself: sm_sweep_host.hpp, the host decides the partial's form with it)
+template <typename CT, int DPL>
+constexpr bool sweep_il()
+{
+    return SWEEP_IL && sizeof(CT) == 1 && DPL % 2 == 0 && !SWEEP_U32;
+}
 
 // NCW: compute waves per workgroup (left halo, NCW-2 own, right halo).  Every strip
 // recomputes 2 halo waves' columns, so wider strips cost fewer instructions per own
@@ -509,7 +526,10 @@ __global__ void __launch_bounds__((sweep_threads<VL, DPL, NCW_, MODE>())) k_swee
     constexpr int LPW = G::LPW, NCW = G::NCW, HB = G::HB, NCOL = G::NCOL, COLS = G::COLS, CW = G::CW, D = G::D;
     constexpr int NG = G::NG, SNG = G::SNG, PF = G::PF, HM = G::HM, HW = G::HW;
     constexpr int CB = DPL * (int)sizeof(CT);  // cost / E / W bytes per lane and cell
-    __shared__ __attribute__((aligned(16))) uint16_t lv[2][2][COLS][D];  // [buf][A=+dx, B=-dx][col+1][d]
+    constexpr bool IL = sweep_il<CT, DPL>();    // the lanes' words interleaved (SWEEP_IL)
+    constexpr int NPW = DPL / 2 > 0 ? DPL / 2 : 1;  // packed words per lane (even DPL)
+    // [buf][A=+dx, B=-dx][col+1][lane slice of DPL, in word order (pk_slot)]
+    __shared__ __attribute__((aligned(16))) uint16_t lv[2][2][COLS][D];
     __shared__ uint32_t lmin[2][2][COLS];
     // WTA sweeps: each own column's aggregated costs S of the current row
     // (wave-local; the line's first lane reads S[best-1], S[best+1] back)
@@ -559,8 +579,10 @@ __global__ void __launch_bounds__((sweep_threads<VL, DPL, NCW_, MODE>())) k_swee
     for (int i = threadIdx.x; i < 2 * 2 * COLS * D / 2; i += NTH) {
         uint32_t v = 0;
         if (vguess) {
-            const int q = (i / (D / 2)) % COLS, d0 = 2 * (i % (D / 2));
-            if (in_domain_slot(q)) v = (uint32_t)(d0 % 5 + 3 * (q & 1)) | ((uint32_t)((d0 + 1) % 5 + 3 * (q & 1)) << 16);
+            const int q = (i / (D / 2)) % COLS, wi = i % (D / 2);  // word wi of the column: its two disparities
+            const int d0 = IL ? wi / NPW * DPL + pk_disp<NPW, IL>(wi % NPW, 0) : 2 * wi;
+            const int d1 = IL ? wi / NPW * DPL + pk_disp<NPW, IL>(wi % NPW, 1) : 2 * wi + 1;
+            if (in_domain_slot(q)) v = (uint32_t)(d0 % 5 + 3 * (q & 1)) | ((uint32_t)(d1 % 5 + 3 * (q & 1)) << 16);
         }
         reinterpret_cast<uint32_t*>(&lv[0][0][0][0])[i] = v;
     }
@@ -822,8 +844,9 @@ __global__ void __launch_bounds__((sweep_threads<VL, DPL, NCW_, MODE>())) k_swee
                 if (a.ewguess && jlo == 0) {
 #pragma unroll
                     for (int i = 0; i < NP; i++) {
-                        const uint32_t d0 = (uint32_t)(g * DPL + 2 * i);
-                        Lp[i] = ((d0 * 7u + (uint32_t)y) % 61u) | ((((d0 + 1u) * 7u + (uint32_t)y) % 61u) << 16);
+                        const uint32_t d0 = (uint32_t)(g * DPL + pk_disp<NP, IL>(i, 0));
+                        const uint32_t d1 = (uint32_t)(g * DPL + pk_disp<NP, IL>(i, 1));
+                        Lp[i] = ((d0 * 7u + (uint32_t)y) % 61u) | (((d1 * 7u + (uint32_t)y) % 61u) << 16);
                     }
                     uint32_t m = Lp[0];
 #pragma unroll
@@ -842,14 +865,14 @@ __global__ void __launch_bounds__((sweep_threads<VL, DPL, NCW_, MODE>())) k_swee
 #pragma unroll
                         for (int q = 0; q < RawBytes<CB>::WORDS; q++) asm volatile("" : "+v"(cr[k].w[q]) : "v"(mm));
                         uint32_t C[1][NP];
-                        unpack_ct_pk<CT, DPL>(cr[k], C[0]);
+                        unpack_vol_pk<CT, DPL, IL>(cr[k], C[0]);
 #pragma unroll
                         for (int i = 0; i < NP; i++) asm volatile("" : "+v"(C[0][i])::"memory");
                         cr[k].load(rc, coff_at(j + LPF));
                         uint32_t Lq[1][NP], mq[1] = {mm}, Ln[1][NP], mn[1];
 #pragma unroll
                         for (int i = 0; i < NP; i++) Lq[0][i] = Lp[i];
-                        sweep_step2n<VL, NP, H16, 1, DSL>(Lq, mq, C, P1p, P2p, eL, eR, Ln, mn);
+                        sweep_step2n<VL, NP, H16, 1, DSL, IL>(Lq, mq, C, P1p, P2p, eL, eR, Ln, mn);
 #pragma unroll
                         for (int i = 0; i < NP; i++) Lp[i] = Ln[0][i];
                         if constexpr (DSL && RING != 0) {  // the column's value is Lp - (input minimum)
@@ -894,13 +917,13 @@ __global__ void __launch_bounds__((sweep_threads<VL, DPL, NCW_, MODE>())) k_swee
                 uint32_t sv[NP];
                 for (int c = 0; c < wch; c++) chunk(c * LPF, std::integral_constant<int, 0>{});
                 min0(sv);
-                store_pk<CT, NP>(rs, so, sv);  // the state entering the strip
+                store_vol_pk<CT, NP, IL>(rs, so, sv);  // the state entering the strip
                 for (int c = 0; c < half; c++) chunk(w + c * LPF, std::integral_constant<int, 1>{});
                 // the first far-half column: the other line wrote it in the last step of the loop above
                 lds_get_pk<NP>(rp + (CW / 2) * rstep, old);
                 for (int c = 0; c < half; c++) chunk(w + (half + c) * LPF, std::integral_constant<int, 2>{});
                 min0(sv);
-                store_pk<CT, NP>(rs, yl ? so + (uint32_t)(D * sizeof(CT)) : kOOB, sv);  // the far end
+                store_vol_pk<CT, NP, IL>(rs, yl ? so + (uint32_t)(D * sizeof(CT)) : kOOB, sv);  // the far end
                 // the batch's ring rows are complete (LDS only: the state stores need no ordering)
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
                 __hip_atomic_store(&linecnt[li], (uint32_t)(t + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -1087,6 +1110,8 @@ __global__ void __launch_bounds__((sweep_threads<VL, DPL, NCW_, MODE>())) k_swee
         constexpr bool SAT = sizeof(CT) == 2;
         constexpr bool H16 = !SAT && SWEEP_H16;  // census: f16 form of the recurrence and the sums
         constexpr bool DS = H16 && SWEEP_DS;     // deferred subtraction (SWEEP_DS)
+        // MODES 3 / 4: the partial in the lanes' interleaved word order (wave-uniform)
+        const bool pil = IL && (MODE == 3 || MODE == 4) && a.part_il != 0;
         static_assert(!DS || SWEEP_STEPN, "deferred subtraction runs the stage-wise steps");
         auto run = [&](auto role_c) {
             constexpr int ROLE = decltype(role_c)::value;  // 0 left halo (A), 1 own (A, B, V), 2 right halo (B)
@@ -1121,8 +1146,8 @@ __global__ void __launch_bounds__((sweep_threads<VL, DPL, NCW_, MODE>())) k_swee
                 const uint32_t o = (uint32_t)(3 * ((c + 1) & 1));
 #pragma unroll
                 for (int i = 0; i < NP; i++) {
-                    const int d0 = g * DPL + 2 * i;
-                    LVp[i] = ((uint32_t)(d0 % 5) + o) | (((uint32_t)((d0 + 1) % 5) + o) << 16);
+                    const int d0 = g * DPL + pk_disp<NP, IL>(i, 0), d1 = g * DPL + pk_disp<NP, IL>(i, 1);
+                    LVp[i] = ((uint32_t)(d0 % 5) + o) | (((uint32_t)(d1 % 5) + o) << 16);
                 }
                 mVl = o * 0x10001u;
             }
@@ -1140,19 +1165,21 @@ __global__ void __launch_bounds__((sweep_threads<VL, DPL, NCW_, MODE>())) k_swee
                     uint32_t v[NP];
 #pragma unroll
                     for (int i = 0; i < NP; i++) v[i] = pk_sub(sV[i], mV_);
-                    store_pk<CT, NP>(rv, off(0), v);
+                    store_vol_pk<CT, NP, IL>(rv, off(0), v);
 #pragma unroll
                     for (int i = 0; i < NP; i++) v[i] = pk_sub(sA[i], mA_);
-                    store_pk<CT, NP>(rv, off(1), v);
+                    store_vol_pk<CT, NP, IL>(rv, off(1), v);
 #pragma unroll
                     for (int i = 0; i < NP; i++) v[i] = pk_sub(sB[i], mB_);
-                    store_pk<CT, NP>(rv, off(2), v);
+                    store_vol_pk<CT, NP, IL>(rv, off(2), v);
                 }
             };
             // d + 1 of each packed half of this lane (uniqueness window test)
             uint32_t dpk[NP];
 #pragma unroll
-            for (int i = 0; i < NP; i++) dpk[i] = (uint32_t)(g * DPL + 2 * i + 1) * 0x10001u + 0x10000u;
+            for (int i = 0; i < NP; i++)  // (the halves of a word are 1 or, interleaved, NP disparities apart)
+                dpk[i] = (uint32_t)(g * DPL + pk_disp<NP, IL>(i, 0) + 1) * 0x10001u +
+                         ((uint32_t)(pk_disp<NP, IL>(i, 1) - pk_disp<NP, IL>(i, 0)) << 16);
             if constexpr (SWEEP_DYNPRIO && !OWN) __builtin_amdgcn_s_setprio(PRIO_HI);
             for (int b = 0; b < nblk; b++) {
 #pragma unroll
@@ -1166,12 +1193,20 @@ __global__ void __launch_bounds__((sweep_threads<VL, DPL, NCW_, MODE>())) k_swee
                     const uint32_t e = live ? cell(y) : NONE;
                     uint32_t C[NS][NP], Ein[NP], Win[NP], Pin[NP];
 #pragma unroll
-                    for (int h = 0; h < NS; h++) unpack_ct_pk<CT, DPL>(rcs[k][h], C[h]);
+                    for (int h = 0; h < NS; h++) unpack_vol_pk<CT, DPL, IL>(rcs[k][h], C[h]);
                     if constexpr (OWN && EWIN) {
-                        unpack_ct_pk<CT, DPL>(re_[k], Ein);
-                        unpack_ct_pk<CT, DPL>(rw_[k], Win);
+                        unpack_vol_pk<CT, DPL, IL>(re_[k], Ein);
+                        unpack_vol_pk<CT, DPL, IL>(rw_[k], Win);
                     }
-                    if constexpr (OWN && PARTR) unpack_ct_pk<uint16_t, DPL>(rp_[k], Pin);
+                    if constexpr (OWN && PARTR) {
+                        if (pil) {  // the partial in the lanes' own word order (SweepArgs::part_il)
+#pragma unroll
+                            for (int i = 0; i < NP; i++) Pin[i] = rp_[k].w[i];
+                        } else {
+                            unpack_vol_pk<uint16_t, DPL, IL>(rp_[k], Pin);
+                            if constexpr (IL) asm volatile("");  // (a branch, not both forms and a select)
+                        }
+                    }
 #pragma unroll
                     for (int i = 0; i < NP; i++) {  // before the refill (see the u32 loop)
 #pragma unroll
@@ -1204,7 +1239,7 @@ __global__ void __launch_bounds__((sweep_threads<VL, DPL, NCW_, MODE>())) k_swee
                     if constexpr (SWEEP_LDS_FIRST && MODE == 1) __builtin_amdgcn_sched_barrier(0);
                     uint32_t nV[NP], nA[NS][NP], nB[NS][NP], mnV = 0, mnA[NS], mnB[NS];
                     auto step = [&](const uint32_t(&Lp)[NP], uint32_t m, const uint32_t(&Ch)[NP], uint32_t(&Ln)[NP]) {
-                        return sweep_step2<VL, NP, H16, DS>(Lp, m, Ch, P1p, P2p, eL, eR, Ln);
+                        return sweep_step2<VL, NP, H16, DS, IL>(Lp, m, Ch, P1p, P2p, eL, eR, Ln);
                     };
                     if constexpr (OWN) {
                         if constexpr (SWEEP_STEPN) {  // stage-wise over the words (sweep_step2n)
@@ -1214,7 +1249,7 @@ __global__ void __launch_bounds__((sweep_threads<VL, DPL, NCW_, MODE>())) k_swee
                                 Lp1[0][i] = LVp[i];
                                 C1[0][i] = C[0][i];
                             }
-                            sweep_step2n<VL, NP, H16, 1, DS>(Lp1, m1, C1, P1p, P2p, eL, eR, Ln1, mn1);
+                            sweep_step2n<VL, NP, H16, 1, DS, IL>(Lp1, m1, C1, P1p, P2p, eL, eR, Ln1, mn1);
 #pragma unroll
                             for (int i = 0; i < NP; i++) nV[i] = Ln1[0][i];
                             mnV = mn1[0];
@@ -1233,7 +1268,7 @@ __global__ void __launch_bounds__((sweep_threads<VL, DPL, NCW_, MODE>())) k_swee
                         }
                         m2[0] = mA[0];
                         m2[1] = mB[0];
-                        sweep_step2n<VL, NP, H16, 2, DS>(Lp2, m2, C2, P1p, P2p, eL, eR, Ln2, mn2);
+                        sweep_step2n<VL, NP, H16, 2, DS, IL>(Lp2, m2, C2, P1p, P2p, eL, eR, Ln2, mn2);
 #pragma unroll
                         for (int i = 0; i < NP; i++) {
                             nA[0][i] = Ln2[0][i];
@@ -1256,7 +1291,7 @@ __global__ void __launch_bounds__((sweep_threads<VL, DPL, NCW_, MODE>())) k_swee
                                 mn_in[h] = mB[h];
                             }
                         }
-                        sweep_step2n<VL, NP, H16, NS, DS>(Lpn, mn_in, C, P1p, P2p, eL, eR, Lnn, mnn);
+                        sweep_step2n<VL, NP, H16, NS, DS, IL>(Lpn, mn_in, C, P1p, P2p, eL, eR, Lnn, mnn);
 #pragma unroll
                         for (int h = 0; h < NS; h++) {
 #pragma unroll
@@ -1410,7 +1445,7 @@ __global__ void __launch_bounds__((sweep_threads<VL, DPL, NCW_, MODE>())) k_swee
 #pragma unroll
                                 for (int i = 0; i < NP; i++) out[i] = pk_sub(out[i], offs);
                             }
-                            bstore_n<uint32_t, NP, SWEEP_STREAM_AUX>(rp, boff(e, 2), out);
+                            store_vol_pk<uint16_t, NP, IL, SWEEP_STREAM_AUX>(rp, boff(e, 2), out);
                         } else if constexpr (MODE == 3) {
                           const int u = s - wrows;  // the band's own row index (< 0: a vertical warmup row)
                           if (u >= 0) {
@@ -1432,6 +1467,13 @@ __global__ void __launch_bounds__((sweep_threads<VL, DPL, NCW_, MODE>())) k_swee
                             if constexpr (DS) {
 #pragma unroll
                                 for (int i = 0; i < NP; i++) out[i] = pk_sub(out[i], offs);
+                            }
+                            if (!pil) {  // d-contiguous for the other readers (the store itself unconditional)
+                                if constexpr (IL) asm volatile("");  // (a branch, not both forms and a select)
+                                uint32_t pl[NP];
+                                pk_to_plain<NP, IL>(out, pl);
+#pragma unroll
+                                for (int i = 0; i < NP; i++) out[i] = pl[i];
                             }
                             bstore_n<uint32_t, NP, SWEEP_STREAM_AUX>(rp, boff(e, 2), out);
                             // the ring row is read (the fence waits for the LDS read): the lines may reuse it
@@ -1468,8 +1510,9 @@ __global__ void __launch_bounds__((sweep_threads<VL, DPL, NCW_, MODE>())) k_swee
                                 if (pad) {
 #pragma unroll
                                     for (int i = 0; i < NP; i++) {
-                                        const int d0 = g * DPL + 2 * i;
-                                        Sp[i] |= (d0 >= a.Dv ? 0x0000FFFFu : 0u) | (d0 + 1 >= a.Dv ? 0xFFFF0000u : 0u);
+                                        const int d0 = g * DPL + pk_disp<NP, IL>(i, 0);
+                                        constexpr int dh = IL ? NP : 1;  // the word's high half: d0 + dh
+                                        Sp[i] |= (d0 >= a.Dv ? 0x0000FFFFu : 0u) | (d0 + dh >= a.Dv ? 0xFFFF0000u : 0u);
                                     }
                                 }
                             } else {
@@ -1498,15 +1541,30 @@ __global__ void __launch_bounds__((sweep_threads<VL, DPL, NCW_, MODE>())) k_swee
                             uint32_t key = 0xFFFFFFFFu;
 #pragma unroll
                             for (int i = 0; i < NP; i++)
-                                key = min(key, min((Sp[i] << 16) | wta_rank(g * DPL + 2 * i, MODE == 1),
-                                                   (Sp[i] & 0xFFFF0000u) | wta_rank(g * DPL + 2 * i + 1, MODE == 1)));
+                                key = min(key, min((Sp[i] << 16) | wta_rank(g * DPL + pk_disp<NP, IL>(i, 0), MODE == 1),
+                                                   (Sp[i] & 0xFFFF0000u) | wta_rank(g * DPL + pk_disp<NP, IL>(i, 1), MODE == 1)));
                             asm volatile("" ::: "memory");  // u32 / u128 stores, u16 loads of srow: no reordering
                             lds_put_pk<NP>(&srow[(wave - 1) % (NCW - 2)][kl][g * DPL], Sp);
                             asm volatile("" ::: "memory");
                             key = group_min<VL>(key);
                             const uint32_t minS = key >> 16;
                             const int best = wta_unrank(key & 0xFFFF, MODE == 1);  // MODE 1 = 5 paths
-                            const int bm = max(best - 1, 0), bq = min(best + 1, D - 1);
+                            // (srow is in word order: disparity d of the column sits at srow_at(d))
+                            // (DPL a power of two: the low log2 DPL bits of d rotated left by one, three
+                            // operations: bit extract, shift-or, bit-field insert)
+                            auto srow_at = [&](int d) -> int {
+                                if constexpr (!IL) return d;
+                                else if constexpr ((DPL & (DPL - 1)) == 0 && NP > 1) {
+                                    // (written out: the compiler's own selection of the same
+                                    // expression took 8 operations per index)
+                                    uint32_t hb, ro, r;
+                                    asm("v_bfe_u32 %0, %1, %2, 1" : "=v"(hb) : "v"(d), "n"(__builtin_ctz(NP)));
+                                    asm("v_lshl_or_b32 %0, %1, 1, %2" : "=v"(ro) : "v"(d), "v"(hb));
+                                    asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(r) : "n"(DPL - 1), "v"(ro), "v"(d));
+                                    return (int)r;
+                                } else return d / DPL * DPL + pk_slot<NP, IL>(d % DPL);
+                            };
+                            const int bm = srow_at(max(best - 1, 0)), bq = srow_at(min(best + 1, D - 1));
                             const uint32_t Sm = srow[(wave - 1) % (NCW - 2)][kl][bm];
                             const uint32_t Sq = srow[(wave - 1) % (NCW - 2)][kl][bq];
                             // uniqueness: the pixel is rejected iff some d with |d - best| > 1 has

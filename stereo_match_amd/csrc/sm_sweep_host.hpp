@@ -15,6 +15,12 @@ namespace smk {
 #define SWEEP_STATS 0  // sm_sweep.hpp: wait-cycle counters (variant builds)
 #endif
 
+// u8-cost sweeps hold each lane's packed words interleaved (sm_sweep.hpp sweep_il, sm_pk.hpp pk_disp);
+// 0 = the plain layout everywhere (comparison builds)
+#ifndef SWEEP_IL
+#define SWEEP_IL 1
+#endif
+
 struct SweepArgs {
     const uint8_t* cost;  // [pair][H][W1][D] of CT
     size_t cost_pair;     // bytes
@@ -56,6 +62,12 @@ struct SweepArgs {
     // item (i % 8) * xcd_per + i / 8 of the (pair, band, strip) list (items >= xcd_total exit at
     // once), so each XCD holds a run of adjacent strips that share cost rows in its L2
     int xcd_per, xcd_total;
+    // MODES 3 / 4 on u8 costs (interleaved lanes, sm_sweep.hpp SWEEP_IL): 1 = the partial keeps each
+    // lane's words as the sweep holds them (word k of a lane's slice = (d_k, d_k+NP)) instead of
+    // d-contiguous: no conversion at MODE 3's store and MODE 4's load.  The host sets it for the
+    // 8-path lines chain MODE 3 -> k_ew_patch -> MODE 4 where the patch pass runs lines of the
+    // sweeps' geometry (EwPatchArgs::part_il); every other reader of a partial gets it d-contiguous
+    int part_il;
 };
 
 
@@ -180,6 +192,8 @@ struct EwPatchArgs {
     const uint32_t* guard;  // the group's give-up flag: nothing to patch when set (the fallback recomputes)
     unsigned long long* fixes;  // [0] strip segments recomputed, [1] of them never met within the strip (u64 atomics)
     int atom;  // 1: no partial cell can saturate (5 x path_max < 65536): atomic corrections, E and W side by side
+    int part_il;  // 1: the partial's lane slices are interleaved (SweepArgs::part_il; u8 costs, lines of the
+                  // sweeps' geometry, no atomic corrections)
 };
 // Vertical patch after a banded MODE 3 sweep (sm_ew.hpp k_band_patch): each
 // column's S / SE / SW state entering a band (speculative, from the band's warmup rows) is checked

@@ -32,6 +32,8 @@ __global__ void k(uint32_t* out, uint32_t seed)
             else if constexpr (OP == 6) asm volatile("v_pk_min_f16 %0, %1, %2" : "=v"(t) : "v"(v), "s"(s));
             else if constexpr (OP == 7) asm volatile("v_pk_add_f16 %0, %1, %2" : "=v"(t) : "v"(v), "s"(s));
             else if constexpr (OP == 8) asm volatile("v_pk_minimum3_f16 %0, %1, %2, %1" : "=v"(t) : "v"(v), "s"(s));
+            else if constexpr (OP == 9)  // min(w, w with its halves swapped): the swap in op_sel (sm_pk.hpp pk_min_halves)
+                asm volatile("v_pk_minimum3_f16 %0, %1, %1, %1 op_sel:[0,1,1] op_sel_hi:[1,0,0]" : "=v"(t) : "v"(v));
             else t = __builtin_amdgcn_perm(v, s, 0x05040100u);
             a[i] = t;
         }
@@ -93,6 +95,8 @@ int main()
     row<7, 8>("v_pk_add_f16", d);
     row<8, 1>("v_pk_minimum3_f16", d);
     row<8, 8>("v_pk_minimum3_f16", d);
+    row<9, 1>("v_pk_minimum3 op_sel", d);
+    row<9, 8>("v_pk_minimum3 op_sel", d);
     (void)hipFree(d);
     return 0;
 }
