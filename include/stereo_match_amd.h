@@ -509,11 +509,18 @@ int sm_set_debug_flags(sm_ctx* ctx, int flags);
  *   SM_TUNE_EW_WAVES   waves per workgroup of the packed E/W lines: 0 automatic, 1..4.
  *   SM_TUNE_EW_PRIO    issue priority (s_setprio 0..3) of the packed E/W lines' waves.
  *   SM_TUNE_EW_WARMUP  columns each in-sweep E/W strip segment runs before its strip
- *                      (0 automatic: 16; 54 for u16 costs in row bands; 1..4096; rounded up
- *                      to the line loop's load chunk).  Any value is exact (the patch pass
- *                      repairs segments that started wrong); large values cost line work.
- *   SM_TUNE_EW_GUESS   0 the segments start from the zero state; 1 (tests) from a
- *                      deliberately wrong state, so that nearly every segment is repaired.
+ *                      (0 automatic: 9 with the cost-derived start state on u8 costs, else
+ *                      16; 54 for u16 costs in row bands; 1..4096; rounded up to the line
+ *                      loop's load chunk).  Any value is exact (the patch pass repairs
+ *                      segments that started wrong); large values cost line work.
+ *   SM_TUNE_EW_GUESS   0 the segments start from the state SM_TUNE_EW_START selects; 1
+ *                      (tests) from a deliberately wrong state, so that nearly every segment
+ *                      is repaired.
+ *   SM_TUNE_EW_START   start state of the in-sweep E/W strip segments: 0 automatic (u8 costs
+ *                      cost-derived, u16 costs zero), 1 cost-derived (the costs of the 4
+ *                      columns before the first warmup column, minus their minimum, times 8,
+ *                      capped at P2; 2..4: from that many columns), -1 the zero state.  Any
+ *                      value is exact; a better start leaves the patch pass fewer repairs.
  *   SM_TUNE_SWEEP_LINES the fused-sweep engine's horizontal paths: 0 automatic (inside the
  *                      down sweep wherever that instance is built), 1 the same, -1 the E/W
  *                      volume kernel (k_ew) before / beside the sweeps.
@@ -550,6 +557,7 @@ int sm_set_debug_flags(sm_ctx* ctx, int flags);
 #define SM_TUNE_LR_STAGGER 12
 #define SM_TUNE_SWEEP_XCD 13
 #define SM_TUNE_PLY_STAGE 14
+#define SM_TUNE_EW_START 15
 int sm_set_tuning(sm_ctx* ctx, int key, int value);
 
 /* Last error text of ctx (or of the calling thread when ctx == NULL). */

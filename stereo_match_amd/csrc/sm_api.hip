@@ -192,6 +192,7 @@ struct sm_ctx {
     int tune_ew_lanes = 0, tune_sweep_ncw = 0, tune_ew_waves = 0, tune_ew_prio = 0;
     int tune_ew_warmup = 0, tune_sweep_lines = 0;  // in-sweep E/W lines: warmup columns, -1 off / 1 on
     int tune_ew_guess = 0;                         // 1: the lines start from a wrong state (tests)
+    int tune_ew_start = 0;  // SM_TUNE_EW_START: 0 automatic, 1..4 the cost-derived start state, -1 the zero state
     int tune_bands = 0, tune_band_warmup = 0, tune_band_guess = 0;  // MODE 3 row bands (SM_TUNE_BANDS ...)
     int tune_cost_wgs = 0;  // k_sgbm_cost2 workgroups a launch aims for (SM_TUNE_COST_WGS; 0: SGBM_COST2_WGS)
     int tune_ply_stage = 0;  // SM_TUNE_PLY_STAGE: 0 / 1 the PLY rows staged in LDS, -1 written directly
@@ -749,6 +750,7 @@ struct SweepJob {
     size_t st_pair = 0;     // bytes
     int ewarm = 0;          // MODE 3: warmup columns of the E/W segments
     int ewguess = 0;        // MODE 3: 1 = a deliberately wrong start state (tests)
+    int ewstart = 0;        // MODE 3: cost columns of the cost-derived start state (0: the zero state)
     int part_il = 0;        // MODES 3 / 4: the partial's lane slices interleaved (SweepArgs::part_il)
     // MODE 3 row bands (nband > 1: the wide instance)
     int nband = 1, band_h = 0, vwarm = 0, vguess = 0;
@@ -934,6 +936,7 @@ int sweep_pass(sm_ctx* ctx, const Norm& n, const Geo& g, const SweepJob& j, int 
         a.st_pair = j.st_pair;
         a.ewarm = j.ewarm;
         a.ewguess = j.ewguess;
+        a.ewstart = j.ewstart;
         a.part_il = j.part_il;
         a.nband = nb;
         a.band_h = j.band_h;
@@ -1144,15 +1147,29 @@ bool use_lines(sm_ctx* ctx, const Norm& n)
     return sweeps_fit(ctx, n, false, true);
 }
 
-// warmup columns of the E/W strip segments: the speculative state meets the true one within
-// 16 columns on ~98 % of KITTI census segments, 24 on ~97 % of u16 (settings.ini) ones
-// (measured on the synthetic pairs with the numpy oracle); SM_TUNE_EW_WARMUP overrides
-int ew_warmup(const sm_ctx* ctx, const Norm& n)
+// cost columns of the E/W strip segments' cost-derived start state (SweepArgs::ewstart; 0: the
+// zero state).  SM_TUNE_EW_START: -1 the zero state, 1 the default column count, 2..EWS_MAXN that
+// many; automatic: on for u8 (census) costs, where it lets the warmup halve at the same repair
+// rate, off for u16 costs, where it does not hold at a shorter warmup (tools/ew_start_study.py:
+// SGBM costs 11-14 % mismatches at 9 columns against 8-9 % from zero at 18) and is selectable
+int ew_start(const sm_ctx* ctx, const Norm& n)
+{
+    if (ctx->tune_ew_start < 0) return 0;
+    if (ctx->tune_ew_start > 0) return ctx->tune_ew_start == 1 ? smk::EWS_MAXN : ctx->tune_ew_start;
+    return elem_bytes(n) == 1 ? smk::EWS_MAXN : 0;
+}
+
+// warmup columns of the E/W strip segments (rounded up to the line loop's load chunk: 9 columns
+// at the 36-column strips).  From the zero state the speculative state meets the true one within
+// 16 columns on ~98 % of KITTI census segments, 24 on ~97 % of u16 (settings.ini) ones; from the
+// cost-derived state census segments meet it as often within 9 (measured on the synthetic pairs
+// with the numpy oracle, tools/ew_start_study.py); SM_TUNE_EW_WARMUP overrides
+int ew_warmup(const sm_ctx* ctx, const Norm& n, int ewstart)
 {
     if (ctx->tune_ew_warmup > 0) return ctx->tune_ew_warmup;
-    // 16 columns for both cost types (sgbm5, 8 pairs: 6520-6535 pairs/s at 16 against 6444-6469
-    // at 24, the patch pass's extra 4.5 us per pair below the sweep's 6 us saved)
-    (void)n;
+    if (ewstart > 0 && elem_bytes(n) == 1) return 9;
+    // 16 columns for both cost types from the zero state (sgbm5, 8 pairs: 6520-6535 pairs/s at 16
+    // against 6444-6469 at 24, the patch pass's extra 4.5 us per pair below the sweep's 6 us saved)
     return 16;
 }
 
@@ -1208,7 +1225,8 @@ int run_lines(sm_ctx* ctx, const Norm& n, const Geo& g, BufSet& bs, hipStream_t 
     j.st_pair = ((size_t)g.H * f.nwg * 4 * n.D * et + 255) & ~size_t(255);
     if ((rc = ensure(ctx, bs.st, j.st_pair * G)) != SM_OK) return rc;
     j.st = (uint8_t*)bs.st.p;
-    j.ewarm = ew_warmup(ctx, n);
+    j.ewstart = ew_start(ctx, n);
+    j.ewarm = ew_warmup(ctx, n, j.ewstart);
     j.ewguess = ctx->tune_ew_guess;
     // 8 paths on u8 costs: the partial goes from MODE 3 through k_ew_patch to MODE 4 only, so it keeps
     // the sweeps' interleaved lane slices where the patch pass's lines (16 lanes where D % 32 == 0,
@@ -2788,6 +2806,7 @@ int sm_compute_disparity_batch_device(sm_ctx* ctx, const uint8_t* dL, const uint
         ctx->twin->tune_ew_warmup = ctx->tune_ew_warmup;
         ctx->twin->tune_sweep_lines = ctx->tune_sweep_lines;
         ctx->twin->tune_ew_guess = ctx->tune_ew_guess;
+        ctx->twin->tune_ew_start = ctx->tune_ew_start;
         ctx->twin->tune_bands = ctx->tune_bands;
         ctx->twin->tune_band_warmup = ctx->tune_band_warmup;
         ctx->twin->tune_band_guess = ctx->tune_band_guess;
@@ -3916,6 +3935,11 @@ int sm_set_tuning(sm_ctx* ctx, int key, int value)
     case SM_TUNE_EW_GUESS:
         if (value < 0 || value > 1) return fail(ctx, SM_E_ARG, "E/W guess %d: 0 or 1", value);
         ctx->tune_ew_guess = value;
+        break;
+    case SM_TUNE_EW_START:
+        if (value < -1 || value > smk::EWS_MAXN)
+            return fail(ctx, SM_E_ARG, "E/W start state %d: -1, 0, 1 or 2..%d cost columns", value, smk::EWS_MAXN);
+        ctx->tune_ew_start = value;
         break;
     case SM_TUNE_SWEEP_LINES:
         if (value < -1 || value > 1) return fail(ctx, SM_E_ARG, "sweep lines %d: -1, 0 or 1", value);

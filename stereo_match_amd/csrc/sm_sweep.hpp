@@ -208,9 +208,10 @@ constexpr int wide_ncw(int D, int ct_bytes)
 
 // ---- MODE 3: the horizontal paths inside the down sweep.  NLW extra
 // waves per workgroup run each row's E and W lines over the strip's own columns, starting
-// `ewarm` columns outside the strip from the zero state (a speculation: exact once the line's
-// state has met the true one), and leave E + W per own column in an LDS ring of LR rows that
-// the own waves add into the partial.  A line wave's batch t covers RPW rows (an E and a W
+// `ewarm` columns outside the strip from the zero state or a state derived from the costs just
+// before (SweepArgs::ewstart; a speculation: exact once the line's state has met the true one),
+// and leave E + W per own column in an LDS ring of LR rows that the own waves add into the
+// partial.  A line wave's batch t covers RPW rows (an E and a W
 // line each); the waves take part in the compute waves' two barriers per block of HB rows,
 // running at most LEAD rows ahead of the block those waves are in.  Deadlock-free for
 // LR >= LEAD + RPW: before a line wave's barrier pair b it has produced every row below
@@ -829,15 +830,58 @@ __global__ void __launch_bounds__((sweep_threads<VL, DPL, NCW_, MODE>())) k_swee
                 auto coff_at = [&](int j) -> uint32_t {
                     return (uint32_t)(j - jlo) < jspan ? coff + (uint32_t)(j * cstep) : kOOB;
                 };
+                // cost-derived start state (a.ewstart = n > 0): the n cost columns just before step
+                // 0 in the line's direction, loaded ahead of the first ring loads (one memory
+                // latency per batch, not two).  Only where the segment starts inside the domain and
+                // all n columns lie in [0, W1); elsewhere the loads read 0, which gives the zero state
+                const int glo = dir ? c0 : c0 - a.ewstart, ghi = dir ? c0 + a.ewstart : c0;
+                const bool gok = yl && a.ewstart > 0 && glo >= 0 && ghi < W1;
+                RawBytes<CB> gr[EWS_MAXN];
+#pragma unroll
+                for (int i = 0; i < EWS_MAXN; i++) {
+                    gr[i].load(rc, gok && i < a.ewstart ? coff - (uint32_t)((i + 1) * cstep) : kOOB);
+                    asm volatile("" ::: "memory");
+                }
                 RawBytes<CB> cr[LPF];
 #pragma unroll
                 for (int k = 0; k < LPF; k++) {
                     cr[k].load(rc, coff_at(k));
                     asm volatile("" ::: "memory");  // issue order = slot order
                 }
+                // G = min(K (A - min_d A), P2), A the sum of the n columns: minimum 0 and G <= P2, the
+                // min-0 form of a state (what a chunk start of the DS lines expects); any start is
+                // exact (k_ew_patch compares the entering state with the trusted one and recomputes
+                // from the costs), a better one only leaves fewer segments to repair.  In word
+                // order (unpack_vol_pk), u16 integer operations in the f16 form too (8 x 4 x 62 < 2048)
+                // (the arithmetic behind the wave-uniform a.ewstart, so the zero start does not pay for
+                // it; the loads stay unconditional: behind the branch too the u16 D = 160 and D = 48
+                // instances spill)
                 uint32_t Lp[NP], mm = 0, old[NP];
 #pragma unroll
-                for (int i = 0; i < NP; i++) Lp[i] = old[i] = 0;
+                for (int q = 0; q < NP; q++) Lp[q] = old[q] = 0;
+                if (a.ewstart > 0) {
+                    uint32_t A[NP];
+                    unpack_vol_pk<CT, DPL, IL>(gr[0], A);
+#pragma unroll
+                    for (int i = 1; i < EWS_MAXN; i++) {
+                        uint32_t Ci[NP];
+                        unpack_vol_pk<CT, DPL, IL>(gr[i], Ci);
+#pragma unroll
+                        for (int q = 0; q < NP; q++) A[q] = pk_add(A[q], Ci[q]);  // (u16: 4 x 16383 < 2^16)
+                    }
+                    uint32_t m = A[0];
+#pragma unroll
+                    for (int q = 1; q < NP; q++) m = pk_min(m, A[q]);
+                    m = group_min<VL>(pk_min_halves<false>(m));  // replicated halves: u32 minima are exact
+#pragma unroll
+                    for (int q = 0; q < NP; q++) {
+                        uint32_t v = pk_sub(A[q], m);
+                        // u16 costs: clamped so that K v cannot wrap (K v > P2 wherever the clamp acts)
+                        if constexpr (sizeof(CT) == 2) v = pk_min(v, (0xFFFFu >> EWS_KSHIFT) * 0x10001u);
+                        Lp[q] = pk_min(pkw(pkv(v) << pk16{EWS_KSHIFT, EWS_KSHIFT}), P2p);
+                        old[q] = 0;
+                    }
+                }
                 // test mode: a deliberately wrong start state.  Only where the segment starts inside
                 // the domain: one that enters it from outside starts from the entry state (the zero
                 // state over zero costs), which makes the first strip of each path exact

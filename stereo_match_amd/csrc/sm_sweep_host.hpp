@@ -21,6 +21,11 @@ namespace smk {
 #define SWEEP_IL 1
 #endif
 
+// cost-derived start state of MODE 3's E/W segments (SweepArgs::ewstart): cost columns a line
+// wave loads for it at most, and log2 of the factor K (K = 8, n = 4: tools/ew_start_study.py)
+constexpr int EWS_MAXN = 4;
+constexpr int EWS_KSHIFT = 3;
+
 struct SweepArgs {
     const uint8_t* cost;  // [pair][H][W1][D] of CT
     size_t cost_pair;     // bytes
@@ -47,6 +52,10 @@ struct SweepArgs {
     size_t st_pair;  // bytes
     int ewarm;
     int ewguess;  // 0: the zero state; 1 (tests): a deliberately wrong start state, every segment repaired
+    // 0: the segments start from the zero state; n in 1..EWS_MAXN: from the cost-derived state
+    // G = min(K (A - min A), P2), A the sum of the n cost columns before the first warmup column
+    // (segments that start inside the domain with all n columns in it)
+    int ewstart;
     // MODE 3 row bands (one or two pairs per call: DESIGN.md §4.5): workgroup blockIdx.x =
     // band * nwg + strip; band b owns rows [b * band_h, (b + 1) * band_h) and starts vwarm rows
     // above them from the zero state (a speculation: k_band_patch repairs the vertical paths
