@@ -264,6 +264,51 @@ int sm_nlm_denoise_u8_batch_device(sm_ctx* ctx, const uint8_t* d_src, int nimg, 
  * to query n.  Needs no context and no device. */
 int sm_nlm_weight_table(float h, int template_window, int search_window, int32_t* tab, int* n, int* fpm, int* shift);
 
+/* ---- float64 Gaussian filter, image_measure and pyrDown: the two host image
+ * operations left in the reference's scripts: image_measure (disparity_test.py:54-66:
+ * cvtColor(BGR2GRAY), scipy.ndimage.gaussian_filter sigma 5 then 3, img + 30 * (img - blurred))
+ * and cv2.pyrDown (try_try.py:56-57).
+ * A Gaussian axis is given by its half kernel w[0..r], centre first, host memory, computed by the
+ * caller (stereo_match_amd.filters.gaussian_kernel1d states scipy's expressions).  Per axis, for
+ * output index i on a line of length n:
+ *   t = a[i]*w[0];  for j = r..1:  t = t + (a[refl(i-j)] + a[refl(i+j)])*w[j]
+ * every operation rounded to float64, no FMA; refl is scipy's 'reflect' (half-sample symmetric,
+ * any r); axis 0 (rows, wy) over the whole image first, then axis 1 (wx).  With such weights the
+ * result equals scipy.ndimage.gaussian_filter(mode='reflect') bit for bit.  A NULL weight pointer
+ * or r = 0 is the identity on that axis.  r 0..64 (larger: SM_E_UNSUPPORTED); H and W 1..16384;
+ * anything else is SM_E_ARG.  Strides of float64 images count doubles, of uint8 images bytes. */
+/* Images [nimg] at src + i*src_img_stride, rows src_stride apart (>= W); dst is [nimg][H][W],
+ * densely packed.  Synchronous. */
+int sm_gauss2d_f64(sm_ctx* ctx, const double* src, int nimg, size_t src_img_stride, int H, int W, int src_stride,
+                   const double* wy, int ry, const double* wx, int rx, double* dst);
+/* Device pointers, destination strides too; one launch for the batch.  Source and destination
+ * must not overlap.  Asynchronous, on the ctx stream. */
+int sm_gauss2d_f64_batch_device(sm_ctx* ctx, const double* d_src, int nimg, size_t src_img_stride, int H, int W,
+                                int src_stride, const double* wy, int ry, const double* wx, int rx, double* d_dst,
+                                size_t dst_img_stride, int dst_stride);
+/* image_measure of a uint8 BGR image (rows src_stride bytes apart, >= 3*W):
+ *   g = (1868*B + 9617*G + 4899*R + 8192) >> 14   (sm_bgr2gray_u8's bytes, exact as float64)
+ *   a = gauss(g; w1, r1 on both axes);  b = gauss(a; w2, r2 on both axes)
+ *   out = a + alpha*(a - b)                        (subtract, multiply, add, each rounded)
+ * out is float64 [H][W], densely packed.  Synchronous. */
+int sm_image_measure_u8(sm_ctx* ctx, const uint8_t* bgr, int H, int W, int src_stride, const double* w1, int r1,
+                        const double* w2, int r2, double alpha, double* dst);
+/* Image i at d_bgr + i*img_stride_bytes, output at d_dst + i*H*W; two launches for the batch,
+ * the intermediate a in a buffer of the context.  Asynchronous, on the ctx stream. */
+int sm_image_measure_u8_batch_device(sm_ctx* ctx, const uint8_t* d_bgr, int nimg, size_t img_stride_bytes, int H, int W,
+                                     int src_stride, const double* w1, int r1, const double* w2, int r2, double alpha,
+                                     double* d_dst);
+/* cv2.pyrDown(src) with the default size and border, uint8, channels 1 or 3 (interleaved):
+ *   dst[y][x][c] = (sum_{i,j=-2..2} k[i]*k[j]*src[r101(2y+i, H)][r101(2x+j, W)][c] + 128) >> 8
+ * k = (1,4,6,4,1), r101 = BORDER_REFLECT_101; dst is [(H+1)/2][(W+1)/2][channels], densely
+ * packed.  A restatement of OpenCV's documented behaviour; parity with OpenCV unpinned.
+ * Synchronous. */
+int sm_pyr_down_u8(sm_ctx* ctx, const uint8_t* src, int H, int W, int src_stride, int channels, uint8_t* dst);
+/* Device pointers, strides in bytes on both sides; one launch for the batch.  Asynchronous. */
+int sm_pyr_down_u8_batch_device(sm_ctx* ctx, const uint8_t* d_src, int nimg, size_t src_img_stride_bytes, int H, int W,
+                                int src_stride, int channels, uint8_t* d_dst, size_t dst_img_stride_bytes,
+                                int dst_stride);
+
 /* ---- point clouds: the tail of the reference's scripts
  * (disparity_calculation.py:302-320, disparity_test.py:230-265, try_try.py:90-96,
  * mapTo3D_mc_cnn.py:124 ff.): reprojectImageTo3D, cvtColor(BGR2RGB), a disparity-range mask,

@@ -11,6 +11,9 @@ Public surface (mirrors the reference / OpenCV names the reference uses):
   ``disparity_calculation.py:131-210,286-287``
 * :func:`fastNlMeansDenoising` — the denoiser in front of the matcher in the test flow,
   ``disparity_test.py:94-95``
+* :func:`image_measure`, :func:`gaussian_filter`, :func:`pyrDown` — the reference's own smoothing
+  function (``disparity_test.py:54-66,82-83``: scipy's float64 Gaussian, bit for bit) and the
+  ``cv2.pyrDown`` in front of ``try_try.py``'s matcher (``:56-57``)
 * :func:`extract_point_cloud`, :func:`format_ply`, :func:`write_point_cloud` — the masked point
   cloud and its ASCII PLY file, the tail of every script (``disparity_calculation.py:302-320``)
 
@@ -28,6 +31,8 @@ from .rectify import (CALIB_ZERO_DISPARITY, COLOR_BGR2GRAY, CV_32FC1, INTER_LINE
                       initUndistortRectifyMap, rectify_opencv, remap, stereoRectify)
 from .denoise import fastNlMeansDenoising
 from .pointcloud import extract_point_cloud, format_ply, write_point_cloud
+from . import filters
+from .filters import gaussian_filter, image_measure, pyrDown
 
 __all__ = [
     "compute_disparity", "matcher_from_settings", "StereoSGBM", "StereoSGBM_create", "createRightMatcher",
@@ -37,5 +42,6 @@ __all__ = [
     "stereoRectify", "initUndistortRectifyMap", "remap", "cvtColor", "rectify_opencv", "StereoRectifier",
     "CALIB_ZERO_DISPARITY", "CV_32FC1", "INTER_LINEAR", "COLOR_BGR2GRAY", "fastNlMeansDenoising",
     "extract_point_cloud", "format_ply", "write_point_cloud",
+    "filters", "gaussian_filter", "image_measure", "pyrDown",
 ]
 __version__ = "0.1.0"

@@ -139,6 +139,19 @@ _SIGS = {
                                                   _c.c_int, _c.c_float, _c.c_int, _c.c_int, _c.c_void_p]),
     "sm_nlm_weight_table": (_c.c_int, [_c.c_float, _c.c_int, _c.c_int, _c.c_void_p, _c.POINTER(_c.c_int),
                                        _c.POINTER(_c.c_int), _c.POINTER(_c.c_int)]),
+    "sm_gauss2d_f64": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_size_t, _c.c_int, _c.c_int, _c.c_int,
+                                  _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_void_p]),
+    "sm_gauss2d_f64_batch_device": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_size_t, _c.c_int, _c.c_int,
+                                               _c.c_int, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_void_p,
+                                               _c.c_size_t, _c.c_int]),
+    "sm_image_measure_u8": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int,
+                                       _c.c_void_p, _c.c_int, _c.c_double, _c.c_void_p]),
+    "sm_image_measure_u8_batch_device": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_size_t, _c.c_int, _c.c_int,
+                                                    _c.c_int, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int,
+                                                    _c.c_double, _c.c_void_p]),
+    "sm_pyr_down_u8": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p]),
+    "sm_pyr_down_u8_batch_device": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_size_t, _c.c_int, _c.c_int,
+                                               _c.c_int, _c.c_int, _c.c_void_p, _c.c_size_t, _c.c_int]),
     "sm_cloud_extract_batch_device": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_size_t, _c.c_int,
                                                  _c.c_int, _c.c_int, _c.c_int, _c.c_void_p,
                                                  _c.POINTER(SmCloudParams), _c.c_size_t, _c.c_void_p, _c.c_void_p,
@@ -644,6 +657,88 @@ class Engine:
         if rc != SM_OK:
             _raise(rc, None)
         return tab, fpm.value, shift.value
+
+    # -- gaussian_filter, image_measure, pyrDown ---------------------------
+    @staticmethod
+    def _half_kernel(w):
+        """(array kept alive, pointer or None, r) of a half kernel w[0..r] (None: identity)."""
+        if w is None:
+            return None, None, 0
+        w = np.ascontiguousarray(w, np.float64)
+        if w.ndim != 1 or w.size < 1:
+            raise ValueError("a half kernel is a 1-D float64 array w[0..r], centre first")
+        return w, w.ctypes.data, w.size - 1
+
+    def gauss2d(self, src: np.ndarray, wy, wx) -> np.ndarray:
+        """sm_gauss2d_f64 of a float64 [H, W] or [N, H, W] array (any row and image stride,
+        pixels contiguous) with the half kernels ``wy`` (axis 0) and ``wx`` (axis 1)."""
+        if not isinstance(src, np.ndarray) or src.dtype != np.float64 or src.ndim not in (2, 3):
+            raise ValueError("gauss2d: src must be a float64 [H, W] or [N, H, W] array")
+        a = src if src.ndim == 3 else src[None]
+        n, H, W = a.shape
+        ok = a.size == 0 or (a.strides[2] == 8 and a.strides[1] % 8 == 0 and a.strides[1] >= 8 * W and
+                             (n == 1 or (a.strides[0] % 8 == 0 and a.strides[0] >= (H - 1) * a.strides[1] + 8 * W)))
+        if not ok:
+            a = np.ascontiguousarray(a)
+        ky, py, ry = self._half_kernel(wy)
+        kx, px, rx = self._half_kernel(wx)
+        out = np.empty((n, H, W), np.float64)
+        self._check(self._lib.sm_gauss2d_f64(self.ctx, a.ctypes.data if a.size else None, n,
+                                             a.strides[0] // 8 if n > 1 else 0, H, W, a.strides[1] // 8 if a.size else W,
+                                             py, ry, px, rx, out.ctypes.data if out.size else None))
+        return out if src.ndim == 3 else out[0]
+
+    def gauss2d_batch_device(self, d_src: int, nimg: int, src_img_stride: int, H: int, W: int, src_stride: int, wy, wx,
+                             d_dst: int, dst_img_stride: int, dst_stride: int):
+        """Strides count doubles."""
+        ky, py, ry = self._half_kernel(wy)
+        kx, px, rx = self._half_kernel(wx)
+        self._check(self._lib.sm_gauss2d_f64_batch_device(
+            self.ctx, ctypes.c_void_p(d_src), nimg, src_img_stride, H, W, src_stride, py, ry, px, rx,
+            ctypes.c_void_p(d_dst), dst_img_stride, dst_stride))
+
+    def image_measure(self, bgr: np.ndarray, w1, w2, alpha: float) -> np.ndarray:
+        """sm_image_measure_u8 of a uint8 [H, W, 3] image: float64 [H, W]."""
+        if not isinstance(bgr, np.ndarray) or bgr.dtype != np.uint8 or bgr.ndim != 3 or bgr.shape[2] != 3:
+            raise ValueError("image_measure: the image must be a uint8 [H, W, 3] array")
+        bgr = np.ascontiguousarray(bgr)
+        H, W = bgr.shape[:2]
+        k1, p1, r1 = self._half_kernel(w1)
+        k2, p2, r2 = self._half_kernel(w2)
+        out = np.empty((H, W), np.float64)
+        self._check(self._lib.sm_image_measure_u8(self.ctx, bgr.ctypes.data if bgr.size else None, H, W, 3 * W, p1, r1,
+                                                  p2, r2, float(alpha), out.ctypes.data if out.size else None))
+        return out
+
+    def image_measure_batch_device(self, d_bgr: int, nimg: int, img_stride: int, H: int, W: int, src_stride: int, w1,
+                                   w2, alpha: float, d_dst: int):
+        k1, p1, r1 = self._half_kernel(w1)
+        k2, p2, r2 = self._half_kernel(w2)
+        self._check(self._lib.sm_image_measure_u8_batch_device(
+            self.ctx, ctypes.c_void_p(d_bgr), nimg, img_stride, H, W, src_stride, p1, r1, p2, r2, float(alpha),
+            ctypes.c_void_p(d_dst)))
+
+    def pyr_down(self, src: np.ndarray) -> np.ndarray:
+        """sm_pyr_down_u8 of a uint8 [H, W] or [H, W, 3] image (any row stride, pixels contiguous)."""
+        if not isinstance(src, np.ndarray) or src.dtype != np.uint8 or src.ndim not in (2, 3):
+            raise ValueError("pyr_down: src must be a uint8 [H, W] or [H, W, 3] array")
+        cn = 1 if src.ndim == 2 else src.shape[2]
+        H, W = src.shape[:2]
+        if src.size and (src.strides[1] != cn or (src.ndim == 3 and src.strides[2] != 1) or src.strides[0] < W * cn):
+            src = np.ascontiguousarray(src)
+        dH, dW = (H + 1) // 2, (W + 1) // 2
+        out = np.empty((dH, dW) if src.ndim == 2 else (dH, dW, cn), np.uint8)
+        self._check(self._lib.sm_pyr_down_u8(self.ctx, src.ctypes.data if src.size else None, H, W,
+                                             src.strides[0] if src.size else W * cn, cn,
+                                             out.ctypes.data if out.size else None))
+        return out
+
+    def pyr_down_batch_device(self, d_src: int, nimg: int, src_img_stride: int, H: int, W: int, src_stride: int,
+                              channels: int, d_dst: int, dst_img_stride: int, dst_stride: int):
+        """Strides count bytes."""
+        self._check(self._lib.sm_pyr_down_u8_batch_device(
+            self.ctx, ctypes.c_void_p(d_src), nimg, src_img_stride, H, W, src_stride, channels, ctypes.c_void_p(d_dst),
+            dst_img_stride, dst_stride))
 
     # -- StereoBM -------------------------------------------------------------------
     def bm_compute(self, left: np.ndarray, right: np.ndarray, params: "SmBmParams") -> np.ndarray:

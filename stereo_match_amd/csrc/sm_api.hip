@@ -34,6 +34,7 @@
 #include "sm_reproject.hpp"
 #include "sm_rectify.hpp"
 #include "sm_nlm.hpp"
+#include "sm_filter.hpp"
 #include "sm_cloud.hpp"
 #include "sm_bm.hpp"
 #include "sm_wide.hpp"
@@ -151,6 +152,7 @@ struct sm_ctx {
     // point clouds (sm_cloud.hpp): block totals and their scans of the extraction (cl_) and the
     // PLY formatter (ply_); vertices, colours and the PLY body of the host and fused entry points
     DevBuf cl_tot, cl_off, ply_tot, ply_off, cl_verts, cl_colors, cl_out;
+    DevBuf flt_a;  // image_measure: the first Gaussian's result, [img][H][W] float64
     DevBuf wls_num, wls_den, wls_inter, wls_w, wls_disp[2], wls_out;  // WLS scratch
     DevBuf wls_R, wls_IT;         // WLS: Thomas pivots / elimination factors of every pass
     hipStream_t wls_stream = nullptr;  // compute_disparity: WLS weights + pivots beside the matchers
@@ -2491,7 +2493,7 @@ void sm_destroy(sm_ctx* ctx)
                       &ctx->bm_cost, &ctx->hop,     &ctx->sweep_err, &ctx->wls_R,      &ctx->wls_IT,
                       &ctx->volwin,  &ctx->rm_src,  &ctx->rm_mapx,   &ctx->rm_mapy,     &ctx->rm_dst,
                       &ctx->rm_gray, &ctx->nlm_tab, &ctx->cl_tot,    &ctx->cl_off,      &ctx->ply_tot,
-                      &ctx->ply_off, &ctx->cl_verts, &ctx->cl_colors, &ctx->cl_out};
+                      &ctx->ply_off, &ctx->cl_verts, &ctx->cl_colors, &ctx->cl_out,      &ctx->flt_a};
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (auto& bs : ctx->set) {
@@ -3324,6 +3326,218 @@ int sm_nlm_denoise_u8(sm_ctx* ctx, const uint8_t* src, int H, int W, int src_str
     {
         StageTimer t_(ctx, ctx->stream, SM_STAGE_D2H, 1);
         HIP_TRY(ctx, hipMemcpyAsync(dst, ctx->rm_gray.p, npx, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return SM_OK;
+}
+
+// ---- gaussian_filter, image_measure and pyrDown (sm_filter.hpp)
+namespace {
+
+// the half kernel of one axis into the kernel arguments; NULL or r = 0: the identity
+int gauss_axis(sm_ctx* ctx, const char* who, const char* axis, const double* w, int r, double* out, int& r_out)
+{
+    if (r < 0) return fail(ctx, SM_E_ARG, "%s: radius %d of axis %s < 0", who, r, axis);
+    if (r > smk::GF_MAX_R)
+        return fail(ctx, SM_E_UNSUPPORTED, "%s: radius %d of axis %s not built: 0..%d", who, r, axis, smk::GF_MAX_R);
+    if (!w || r == 0) {
+        out[0] = 1.0;
+        r_out = 0;
+        return SM_OK;
+    }
+    std::copy(w, w + r + 1, out);
+    r_out = r;
+    return SM_OK;
+}
+
+int filter_image_check(sm_ctx* ctx, const char* who, const void* src, const void* dst, int nimg, int H, int W)
+{
+    if (H <= 0 || W <= 0 || H > kRectMaxDim || W > kRectMaxDim)
+        return fail(ctx, SM_E_ARG, "%s: size %d x %d outside 1..%d", who, W, H, kRectMaxDim);
+    if (!src || !dst) return fail(ctx, SM_E_ARG, "%s: NULL argument", who);
+    if (nimg < 0 || nimg > 65535) return fail(ctx, SM_E_ARG, "%s: nimg %d", who, nimg);
+    return SM_OK;
+}
+
+// elements from the first image's first to the last image's last
+size_t filter_span(int nimg, size_t img_stride, int H, int W, int stride)
+{
+    return (size_t)(nimg - 1) * img_stride + (size_t)(H - 1) * stride + (size_t)W;
+}
+
+extern "C++" template <bool BGR, bool UNSHARP>
+int gauss_launch(sm_ctx* ctx, const smk::GaussArgs& a, int nimg)
+{
+    const size_t lds = smk::gauss_lds_bytes(a.ry, a.rx);
+    const auto kernel = smk::k_gauss2d_f64<BGR, UNSHARP>;
+    if (lds > 48 * 1024)  // above the default limit of dynamic LDS
+        HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const dim3 grid((a.W + smk::GF_TW - 1) / smk::GF_TW, (a.H + smk::GF_TH - 1) / smk::GF_TH, nimg);
+    hipLaunchKernelGGL(kernel, grid, dim3(smk::GF_THREADS), lds, ctx->stream, a);
+    HIP_TRY(ctx, hipGetLastError());
+    return SM_OK;
+}
+
+}  // namespace
+
+int sm_gauss2d_f64_batch_device(sm_ctx* ctx, const double* d_src, int nimg, size_t src_img_stride, int H, int W,
+                                int src_stride, const double* wy, int ry, const double* wx, int rx, double* d_dst,
+                                size_t dst_img_stride, int dst_stride)
+{
+    if (!ctx) return fail(nullptr, SM_E_ARG, "ctx is NULL");
+    int rc;
+    if ((rc = filter_image_check(ctx, "gauss2d", d_src, d_dst, nimg, H, W)) != SM_OK) return rc;
+    if (src_stride < W || dst_stride < W)
+        return fail(ctx, SM_E_ARG, "gauss2d: row stride %d / %d < %d", src_stride, dst_stride, W);
+    if (nimg > 1 && (src_img_stride < filter_span(1, 0, H, W, src_stride) ||
+                     dst_img_stride < filter_span(1, 0, H, W, dst_stride)))
+        return fail(ctx, SM_E_ARG, "gauss2d: image stride %zu / %zu smaller than one image", src_img_stride,
+                    dst_img_stride);
+    smk::GaussArgs a{};
+    if ((rc = gauss_axis(ctx, "gauss2d", "0", wy, ry, a.wy, a.ry)) != SM_OK) return rc;
+    if ((rc = gauss_axis(ctx, "gauss2d", "1", wx, rx, a.wx, a.rx)) != SM_OK) return rc;
+    if (nimg == 0) return SM_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    a.src = d_src, a.dst = d_dst, a.src_img_stride = src_img_stride, a.dst_img_stride = dst_img_stride;
+    a.H = H, a.W = W, a.src_stride = src_stride, a.dst_stride = dst_stride;
+    return gauss_launch<false, false>(ctx, a, nimg);
+}
+
+int sm_gauss2d_f64(sm_ctx* ctx, const double* src, int nimg, size_t src_img_stride, int H, int W, int src_stride,
+                   const double* wy, int ry, const double* wx, int rx, double* dst)
+{
+    if (!ctx) return fail(nullptr, SM_E_ARG, "ctx is NULL");
+    int rc;
+    if ((rc = filter_image_check(ctx, "gauss2d", src, dst, nimg, H, W)) != SM_OK) return rc;
+    if (src_stride < W) return fail(ctx, SM_E_ARG, "gauss2d: row stride %d < %d", src_stride, W);
+    if (nimg == 0) return SM_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t sb = filter_span(nimg, src_img_stride, H, W, src_stride) * 8, db = (size_t)nimg * H * W * 8;
+    if ((rc = ensure(ctx, ctx->rm_src, sb)) != SM_OK) return rc;
+    if ((rc = ensure(ctx, ctx->rm_dst, db)) != SM_OK) return rc;
+    {
+        StageTimer t_(ctx, ctx->stream, SM_STAGE_H2D, 1);
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->rm_src.p, src, sb, hipMemcpyHostToDevice, ctx->stream));
+    }
+    if ((rc = sm_gauss2d_f64_batch_device(ctx, (const double*)ctx->rm_src.p, nimg, src_img_stride, H, W, src_stride,
+                                          wy, ry, wx, rx, (double*)ctx->rm_dst.p, (size_t)H * W, W)) != SM_OK)
+        return rc;
+    {
+        StageTimer t_(ctx, ctx->stream, SM_STAGE_D2H, 1);
+        HIP_TRY(ctx, hipMemcpyAsync(dst, ctx->rm_dst.p, db, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return SM_OK;
+}
+
+int sm_image_measure_u8_batch_device(sm_ctx* ctx, const uint8_t* d_bgr, int nimg, size_t img_stride_bytes, int H, int W,
+                                     int src_stride, const double* w1, int r1, const double* w2, int r2, double alpha,
+                                     double* d_dst)
+{
+    if (!ctx) return fail(nullptr, SM_E_ARG, "ctx is NULL");
+    int rc;
+    if ((rc = filter_image_check(ctx, "image_measure", d_bgr, d_dst, nimg, H, W)) != SM_OK) return rc;
+    if (src_stride < W * 3) return fail(ctx, SM_E_ARG, "image_measure: src_stride %d < %d", src_stride, W * 3);
+    if (nimg > 1 && img_stride_bytes < (size_t)(H - 1) * src_stride + (size_t)W * 3)
+        return fail(ctx, SM_E_ARG, "image_measure: img_stride_bytes %zu smaller than one image", img_stride_bytes);
+    smk::GaussArgs a{}, b{};
+    if ((rc = gauss_axis(ctx, "image_measure", "0 and 1 of the first filter", w1, r1, a.wy, a.ry)) != SM_OK) return rc;
+    if ((rc = gauss_axis(ctx, "image_measure", "0 and 1 of the second filter", w2, r2, b.wy, b.ry)) != SM_OK) return rc;
+    std::copy(a.wy, a.wy + a.ry + 1, a.wx), a.rx = a.ry;
+    std::copy(b.wy, b.wy + b.ry + 1, b.wx), b.rx = b.ry;
+    if (nimg == 0) return SM_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t npx = (size_t)H * W;
+    // a reallocation waits for the whole device (ensure), so no earlier launch still uses flt_a
+    if ((rc = ensure(ctx, ctx->flt_a, (size_t)nimg * npx * 8)) != SM_OK) return rc;
+    a.src = d_bgr, a.dst = (double*)ctx->flt_a.p, a.src_img_stride = img_stride_bytes, a.dst_img_stride = npx;
+    a.H = H, a.W = W, a.src_stride = src_stride, a.dst_stride = W;
+    if ((rc = gauss_launch<true, false>(ctx, a, nimg)) != SM_OK) return rc;
+    b.src = ctx->flt_a.p, b.dst = d_dst, b.src_img_stride = npx, b.dst_img_stride = npx;
+    b.H = H, b.W = W, b.src_stride = W, b.dst_stride = W, b.alpha = alpha;
+    return gauss_launch<false, true>(ctx, b, nimg);
+}
+
+int sm_image_measure_u8(sm_ctx* ctx, const uint8_t* bgr, int H, int W, int src_stride, const double* w1, int r1,
+                        const double* w2, int r2, double alpha, double* dst)
+{
+    if (!ctx) return fail(nullptr, SM_E_ARG, "ctx is NULL");
+    int rc;
+    if ((rc = filter_image_check(ctx, "image_measure", bgr, dst, 1, H, W)) != SM_OK) return rc;
+    if (src_stride < W * 3) return fail(ctx, SM_E_ARG, "image_measure: src_stride %d < %d", src_stride, W * 3);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t sb = (size_t)(H - 1) * src_stride + (size_t)W * 3, db = (size_t)H * W * 8;
+    if ((rc = ensure(ctx, ctx->rm_src, sb)) != SM_OK) return rc;
+    if ((rc = ensure(ctx, ctx->rm_dst, db)) != SM_OK) return rc;
+    {
+        StageTimer t_(ctx, ctx->stream, SM_STAGE_H2D, 1);
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->rm_src.p, bgr, sb, hipMemcpyHostToDevice, ctx->stream));
+    }
+    if ((rc = sm_image_measure_u8_batch_device(ctx, (const uint8_t*)ctx->rm_src.p, 1, 0, H, W, src_stride, w1, r1, w2,
+                                               r2, alpha, (double*)ctx->rm_dst.p)) != SM_OK)
+        return rc;
+    {
+        StageTimer t_(ctx, ctx->stream, SM_STAGE_D2H, 1);
+        HIP_TRY(ctx, hipMemcpyAsync(dst, ctx->rm_dst.p, db, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return SM_OK;
+}
+
+int sm_pyr_down_u8_batch_device(sm_ctx* ctx, const uint8_t* d_src, int nimg, size_t src_img_stride_bytes, int H, int W,
+                                int src_stride, int channels, uint8_t* d_dst, size_t dst_img_stride_bytes,
+                                int dst_stride)
+{
+    if (!ctx) return fail(nullptr, SM_E_ARG, "ctx is NULL");
+    int rc;
+    if ((rc = filter_image_check(ctx, "pyrDown", d_src, d_dst, nimg, H, W)) != SM_OK) return rc;
+    if (channels != 1 && channels != 3) return fail(ctx, SM_E_ARG, "pyrDown: channels %d (1 or 3)", channels);
+    const int dH = (H + 1) / 2, dW = (W + 1) / 2;
+    if (src_stride < W * channels || dst_stride < dW * channels)
+        return fail(ctx, SM_E_ARG, "pyrDown: row stride %d / %d < %d / %d", src_stride, dst_stride, W * channels,
+                    dW * channels);
+    if (nimg > 1 && (src_img_stride_bytes < filter_span(1, 0, H, W * channels, src_stride) ||
+                     dst_img_stride_bytes < filter_span(1, 0, dH, dW * channels, dst_stride)))
+        return fail(ctx, SM_E_ARG, "pyrDown: image stride %zu / %zu smaller than one image", src_img_stride_bytes,
+                    dst_img_stride_bytes);
+    if (nimg == 0) return SM_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    smk::PyrArgs a{};
+    a.src = d_src, a.dst = d_dst, a.src_img_stride = src_img_stride_bytes, a.dst_img_stride = dst_img_stride_bytes;
+    a.H = H, a.W = W, a.dH = dH, a.dW = dW, a.src_stride = src_stride, a.dst_stride = dst_stride;
+    a.vec = ((uintptr_t)d_dst | (uintptr_t)dst_stride | (nimg > 1 ? dst_img_stride_bytes : 0)) % 4 == 0;
+    const dim3 grid(((dW * channels + 3) / 4 + 255) / 256, dH, nimg);
+    if (channels == 1)
+        hipLaunchKernelGGL(smk::k_pyr_down_u8<1>, grid, dim3(256), 0, ctx->stream, a);
+    else
+        hipLaunchKernelGGL(smk::k_pyr_down_u8<3>, grid, dim3(256), 0, ctx->stream, a);
+    HIP_TRY(ctx, hipGetLastError());
+    return SM_OK;
+}
+
+int sm_pyr_down_u8(sm_ctx* ctx, const uint8_t* src, int H, int W, int src_stride, int channels, uint8_t* dst)
+{
+    if (!ctx) return fail(nullptr, SM_E_ARG, "ctx is NULL");
+    int rc;
+    if ((rc = filter_image_check(ctx, "pyrDown", src, dst, 1, H, W)) != SM_OK) return rc;
+    if (channels != 1 && channels != 3) return fail(ctx, SM_E_ARG, "pyrDown: channels %d (1 or 3)", channels);
+    if (src_stride < W * channels) return fail(ctx, SM_E_ARG, "pyrDown: src_stride %d < %d", src_stride, W * channels);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int dH = (H + 1) / 2, dW = (W + 1) / 2;
+    const size_t sb = (size_t)(H - 1) * src_stride + (size_t)W * channels, db = (size_t)dH * dW * channels;
+    if ((rc = ensure(ctx, ctx->rm_src, sb)) != SM_OK) return rc;
+    if ((rc = ensure(ctx, ctx->rm_dst, db)) != SM_OK) return rc;
+    {
+        StageTimer t_(ctx, ctx->stream, SM_STAGE_H2D, 1);
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->rm_src.p, src, sb, hipMemcpyHostToDevice, ctx->stream));
+    }
+    if ((rc = sm_pyr_down_u8_batch_device(ctx, (const uint8_t*)ctx->rm_src.p, 1, 0, H, W, src_stride, channels,
+                                          (uint8_t*)ctx->rm_dst.p, 0, dW * channels)) != SM_OK)
+        return rc;
+    {
+        StageTimer t_(ctx, ctx->stream, SM_STAGE_D2H, 1);
+        HIP_TRY(ctx, hipMemcpyAsync(dst, ctx->rm_dst.p, db, hipMemcpyDeviceToHost, ctx->stream));
     }
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return SM_OK;

@@ -175,15 +175,19 @@ def _compute_torch(left, right, prm: SmParams):
 
     if left.shape != right.shape or left.dtype != torch.uint8 or right.dtype != torch.uint8:
         raise ValueError("left/right must be same-shape torch.uint8 tensors")
-    if left.dim() != 2 or left.device != right.device:
-        raise ValueError("left/right must be 2-D tensors on the same device")
+    bgr = left.dim() == 3 and left.shape[2] == 3
+    if not (left.dim() == 2 or bgr) or left.device != right.device:
+        raise ValueError("left/right must be gray [H, W] or BGR [H, W, 3] tensors on the same device")
     left = left.contiguous()
     right = right.contiguous()
-    H, W = left.shape
+    H, W = left.shape[:2]
     out = torch.empty((H, W), dtype=torch.int16, device=left.device)
     eng = _lib.engine(left.device.index or 0)
     eng.set_stream(torch.cuda.current_stream(left.device).cuda_stream)
-    eng.compute_device(left.data_ptr(), right.data_ptr(), H, W, W, prm, out.data_ptr())
+    if bgr:  # as the numpy path: the BGR cost (sm_compute_cn)
+        eng.compute_batch_device(left.data_ptr(), right.data_ptr(), 1, 0, H, W, 3 * W, prm, out.data_ptr(), channels=3)
+    else:
+        eng.compute_device(left.data_ptr(), right.data_ptr(), H, W, W, prm, out.data_ptr())
     return out
 
 
