@@ -587,6 +587,13 @@ int sm_set_debug_flags(sm_ctx* ctx, int flags);
  *   SM_TUNE_PLY_STAGE  the PLY formatter's write pass: 0 automatic / 1 a block's rows staged in
  *                      LDS and streamed out in 16-byte stores, -1 every row straight to global
  *                      memory (the same bytes; DESIGN.md §4.9 has the measurement).
+ *   SM_TUNE_EW_PATCH   where the E/W patch pass of the 8-path lines chain runs: 0 automatic
+ *                      (inside the up + WTA sweep where that sweep runs its wide strips anyway),
+ *                      1 inside the up + WTA sweep (extra waves of its workgroups patch each
+ *                      row before the sweep reaches it; the instances built for it: u8 costs,
+ *                      128 disparities, all pairs of a group in one launch), -1 a launch of its
+ *                      own between the sweeps.  The same results and repair counters either way;
+ *                      other chains (5 paths, u16 costs, row bands) always use the launch.
  * Returns SM_E_ARG for an unknown key or value. */
 #define SM_TUNE_EW_LANES 1
 #define SM_TUNE_SWEEP_NCW 2
@@ -603,6 +610,7 @@ int sm_set_debug_flags(sm_ctx* ctx, int flags);
 #define SM_TUNE_SWEEP_XCD 13
 #define SM_TUNE_PLY_STAGE 14
 #define SM_TUNE_EW_START 15
+#define SM_TUNE_EW_PATCH 16
 int sm_set_tuning(sm_ctx* ctx, int key, int value);
 
 /* Last error text of ctx (or of the calling thread when ctx == NULL). */

@@ -824,6 +824,7 @@ class Engine:
     TUNE_BANDS, TUNE_BAND_WARMUP, TUNE_BAND_GUESS, TUNE_COST_WGS, TUNE_LR_STAGGER, TUNE_SWEEP_XCD = 8, 9, 10, 11, 12, 13
     TUNE_PLY_STAGE = 14
     TUNE_EW_START = 15
+    TUNE_EW_PATCH = 16
 
     def set_tuning(self, key: int, value: int):
         """Launch-shape knob (include/stereo_match_amd.h sm_set_tuning); 0 = automatic."""

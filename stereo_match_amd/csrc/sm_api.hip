@@ -195,6 +195,7 @@ struct sm_ctx {
     int tune_ew_warmup = 0, tune_sweep_lines = 0;  // in-sweep E/W lines: warmup columns, -1 off / 1 on
     int tune_ew_guess = 0;                         // 1: the lines start from a wrong state (tests)
     int tune_ew_start = 0;  // SM_TUNE_EW_START: 0 automatic, 1..4 the cost-derived start state, -1 the zero state
+    int tune_ew_patch = 0;  // SM_TUNE_EW_PATCH: 0 automatic, 1 the E/W patch inside the up sweep, -1 its own launch
     int tune_bands = 0, tune_band_warmup = 0, tune_band_guess = 0;  // MODE 3 row bands (SM_TUNE_BANDS ...)
     int tune_cost_wgs = 0;  // k_sgbm_cost2 workgroups a launch aims for (SM_TUNE_COST_WGS; 0: SGBM_COST2_WGS)
     int tune_ply_stage = 0;  // SM_TUNE_PLY_STAGE: 0 / 1 the PLY rows staged in LDS, -1 written directly
@@ -754,6 +755,8 @@ struct SweepJob {
     int ewguess = 0;        // MODE 3: 1 = a deliberately wrong start state (tests)
     int ewstart = 0;        // MODE 3: cost columns of the cost-derived start state (0: the zero state)
     int part_il = 0;        // MODES 3 / 4: the partial's lane slices interleaved (SweepArgs::part_il)
+    unsigned long long* fixes = nullptr;  // host mode 5: the in-sweep patch's counters (SweepArgs::fixes)
+    int pnwg = 0, pcw = 0;                // host mode 5: MODE 3's strips (SweepArgs::pnwg, pcw)
     // MODE 3 row bands (nband > 1: the wide instance)
     int nband = 1, band_h = 0, vwarm = 0, vguess = 0;
     uint8_t* vst = nullptr;
@@ -908,7 +911,9 @@ int sweep_pass(sm_ctx* ctx, const Norm& n, const Geo& g, const SweepJob& j, int 
     const int nblk = banded ? (j.band_h + j.vwarm + si.hb - 1) / si.hb : (g.H + si.hb - 1) / si.hb;
     // ablation / test flag 8192: one pair per sweep launch (exercises the chunked launches)
     const int per_launch = (ctx->dbg_flags & DBG_SWEEP1) ? 1 : std::max(1, std::min(j.G, cap / (nwg * nb)));
-    const size_t hop_pair = (size_t)nwg * nb * 2 * nblk * si.ngr;
+    // (host mode 5: + one flag granule per image row behind the pair's snapshots, SweepArgs::flag_off)
+    const size_t hop_snap = (size_t)nwg * nb * 2 * nblk * si.ngr;
+    const size_t hop_pair = hop_snap + (mode == 5 ? (size_t)g.H : 0);
     const size_t hop_bytes = hop_pair * 8 * per_launch;
     if (hop_pair * 8 > smk::kMaxRecords) return fail(ctx, SM_E_UNSUPPORTED, "sweep: boundary buffer too large");
     int rc;
@@ -940,6 +945,10 @@ int sweep_pass(sm_ctx* ctx, const Norm& n, const Geo& g, const SweepJob& j, int 
         a.ewguess = j.ewguess;
         a.ewstart = j.ewstart;
         a.part_il = j.part_il;
+        a.fixes = mode == 5 ? j.fixes : nullptr;
+        a.flag_off = mode == 5 ? hop_snap : 0;
+        a.pnwg = j.pnwg;
+        a.pcw = j.pcw;
         a.nband = nb;
         a.band_h = j.band_h;
         a.vwarm = j.vwarm;
@@ -1207,6 +1216,10 @@ int band_warmup(const sm_ctx* ctx, const Norm& n)
     return elem_bytes(n) == 1 ? 16 : 24;
 }
 
+// SM_TUNE_EW_PATCH 0: where the E/W patch pass runs by default (1: inside the up sweep where its
+// instance is built, 0: its own launch).  Measurements: DESIGN.md §8.
+constexpr bool kEwPatchInSweep = true;
+
 int run_lines(sm_ctx* ctx, const Norm& n, const Geo& g, BufSet& bs, hipStream_t ws, uint32_t* gflag)
 {
     const int G = g.G;
@@ -1251,6 +1264,22 @@ int run_lines(sm_ctx* ctx, const Norm& n, const Geo& g, BufSet& bs, hipStream_t 
     ctx->line_groups++;
     ctx->line_strips += (long long)f.nwg * G;
     const bool fb_side = n.ndirs == 5 && ws == ctx->stream && !(ctx->dbg_flags & DBG_NO_FALLBACK);
+    // the E/W patch pass inside the up + WTA sweep (host mode 5: MODE 4 with patch waves, DESIGN.md
+    // §4.4 addendum) instead of a launch between the sweeps: the 8-path u8 chain with the
+    // interleaved partial, all G pairs in one launch (the patch waves take MODE 3's strips from
+    // pnwg / pcw: the two sweeps' instances may differ).  SM_TUNE_EW_PATCH: 1 wherever that
+    // instance is built, -1 never; automatic: where the plain up sweep would run the same wide
+    // strips, so no launch group changes its sweep instance for it.
+    bool patch_in_sweep = false;
+    if (n.ndirs == 8 && et == 1 && j.part_il && j.nband <= 1 && !(ctx->dbg_flags & DBG_SWEEP1) &&
+        (ctx->tune_ew_patch > 0 || (ctx->tune_ew_patch == 0 && kEwPatchInSweep))) {
+        SweepFit f5, f4;
+        patch_in_sweep = sweep_capacity(ctx, n, 5, G, f5) && f5.si.impl == 1 && f5.cap / std::max(f5.nwg, 1) >= G;
+        if (patch_in_sweep && ctx->tune_ew_patch == 0)
+            patch_in_sweep = sweep_capacity(ctx, n, 4, G, f4) && f4.si.impl == 1 && f4.si.ncw == f5.si.ncw;
+        j.pnwg = f.nwg;
+        j.pcw = f.si.cw;
+    }
     {
         StageTimer t(ctx, ctx->stream, SM_STAGE_PATHS, G);
         {
@@ -1317,10 +1346,11 @@ int run_lines(sm_ctx* ctx, const Norm& n, const Geo& g, BufSet& bs, hipStream_t 
             if (rc != SM_OK) return rc;
             HIP_TRY(ctx, hipEventRecord(ctx->ev_fb_join, ctx->side));
         }
-        if (!ew_side) {
+        if (!ew_side && !patch_in_sweep) {
             StageTimer th(ctx, ctx->stream, SM_STAGE_HORIZONTAL, G);
             if ((rc = ew_patch(ctx->stream)) != SM_OK) return rc;
         }
+        j.fixes = pa.fixes;
         if (j.nband > 1) {  // then the vertical chains at the band boundaries (after: both touch the partial)
             smk::BandPatchArgs ba{};
             ba.cost = j.cost;
@@ -1358,7 +1388,7 @@ int run_lines(sm_ctx* ctx, const Norm& n, const Geo& g, BufSet& bs, hipStream_t 
             StreamSwap sw(ctx, ws);
             StageTimer t(ctx, ctx->stream, SM_STAGE_WTA, G);
             StageTimer ts(ctx, ctx->stream, SM_STAGE_SWEEP_WTA, G);
-            if ((rc = sweep_pass(ctx, n, g, j, 4)) != SM_OK) return rc;
+            if ((rc = sweep_pass(ctx, n, g, j, patch_in_sweep ? 5 : 4)) != SM_OK) return rc;
         }
         return sweep_finish(ctx, n, g, bs, ws, gflag);
     }
@@ -4154,6 +4184,10 @@ int sm_set_tuning(sm_ctx* ctx, int key, int value)
         if (value < -1 || value > smk::EWS_MAXN)
             return fail(ctx, SM_E_ARG, "E/W start state %d: -1, 0, 1 or 2..%d cost columns", value, smk::EWS_MAXN);
         ctx->tune_ew_start = value;
+        break;
+    case SM_TUNE_EW_PATCH:
+        if (value < -1 || value > 1) return fail(ctx, SM_E_ARG, "E/W patch placement %d: -1, 0 or 1", value);
+        ctx->tune_ew_patch = value;
         break;
     case SM_TUNE_SWEEP_LINES:
         if (value < -1 || value > 1) return fail(ctx, SM_E_ARG, "sweep lines %d: -1, 0 or 1", value);

@@ -155,8 +155,16 @@ __global__ void __launch_bounds__(256) k_ew(EwArgs a)
 // corrections are u32 atomic adds of (true - applied) per u16 pair as one signed addend, exact
 // in any order while every half stays a valid sum (band patch argument), so the partial is never
 // read and E and W of a row run in two waves side by side (twice the waves, no E -> W order).
-template <int VL, int NP, typename CT, bool ATOM = false>
-__global__ void __launch_bounds__(256) k_ew_patch(EwPatchArgs a)
+//
+// ew_patch_row: the pass over one image row of one pair by one wave, directions dir0 .. dir1 - 1
+// (k_ew_patch: one wave per row; sm_sweep.hpp: the patch waves of the up + WTA sweep).  `openm`:
+// kPatchMaxChunks words of LDS the calling wave owns (phase A's open strips).  PUB (the in-sweep
+// pass, whose repaired cells another workgroup reads inside the launch): every load and store of
+// the partial carries sc1 (write-through stores; the wave's own re-reads of a cell bypass the L1);
+// the caller drains the stores and publishes the row.  RC_: columns of a repaired segment loaded
+// together (0: by cost type).
+template <int VL, int NP, typename CT, bool ATOM = false, bool PUB = false, int RC_ = 0>
+__device__ __forceinline__ void ew_patch_row(const EwPatchArgs& a, size_t pair, int y, int dir0, int dir1, uint64_t* openm)
 {
     constexpr int LPW = 64 / VL, DPL = 2 * NP, D = VL * DPL;
     constexpr int CB = DPL * (int)sizeof(CT);
@@ -167,16 +175,12 @@ __global__ void __launch_bounds__(256) k_ew_patch(EwPatchArgs a)
     // chunk of LPW * KU path positions, all loads of a chunk in flight together
     constexpr int KU = 8;
     constexpr int CHUNK = LPW * KU;
-    constexpr int RC = EW_PATCH_RC ? EW_PATCH_RC : sizeof(CT) == 1 ? 8 : 16;  // columns of a repaired segment loaded together
-    if (a.guard && __hip_atomic_load(a.guard, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) return;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    constexpr int RC = RC_ ? RC_ : EW_PATCH_RC ? EW_PATCH_RC : sizeof(CT) == 1 ? 8 : 16;  // columns of a repaired segment loaded together
+    constexpr int PAUX = PUB ? 16 : 0;  // cache policy of the partial's loads and stores (16 = sc1)
+    static_assert(!(PUB && ATOM), "the published pass reads and writes the partial itself");
+    const int lane = threadIdx.x & 63;
     const int g = lane % VL, kl = lane / VL;
-    const int yw = (int)blockIdx.x * 4 + wave;  // one wave per image row (ATOM: per row and direction)
-    const int y = ATOM ? yw >> 1 : yw;           // (wave-uniform)
-    const int dir0 = ATOM ? (yw & 1) : 0, dir1 = ATOM ? dir0 + 1 : 2;
-    const size_t pair = blockIdx.y;
     const int H = a.H, W1 = a.W1, nwg = a.nwg, CW = a.cw;
-    if (y >= H) return;
     const uint64_t cells = (uint64_t)H * W1 * D;
     const rsrc_t rc = make_rsrc(a.cost + pair * a.cost_pair, cells * sizeof(CT));
     const rsrc_t rp = make_rsrc((const uint8_t*)a.part + pair * a.part_pair, cells * 2);
@@ -234,7 +238,7 @@ __global__ void __launch_bounds__(256) k_ew_patch(EwPatchArgs a)
         auto issue1 = [&](int u, int o) {  // slot u <- column o of the walk
             const int c = dir ? x0 + CW - 1 - o : x0 + o;
             cc[u].load(rc, o < ncol ? cell(c) * (uint32_t)sizeof(CT) : kOOB);
-            if constexpr (!ATOM) pb[u].load(rp, o < ncol ? cell(c) * 2u : kOOB);
+            if constexpr (!ATOM) pb[u].template load<PAUX>(rp, o < ncol ? cell(c) * 2u : kOOB);
         };
         auto issue = [&](int o0) {
 #pragma unroll
@@ -302,7 +306,7 @@ __global__ void __launch_bounds__(256) k_ew_patch(EwPatchArgs a)
 #pragma unroll
                     for (int q = 0; q < NP; q++) P[q] = t[q];
                 }
-                if constexpr (!ATOM) bstore_n<uint32_t, NP>(rp, cell(c) * 2u, P);
+                if constexpr (!ATOM) bstore_n<uint32_t, NP, PAUX>(rp, cell(c) * 2u, P);
 #pragma unroll
                 for (int q = 0; q < NP; q++) {
                     Lq[0][q] = Ln[0][q];
@@ -356,7 +360,7 @@ __global__ void __launch_bounds__(256) k_ew_patch(EwPatchArgs a)
         auto issue1 = [&](int u, int o) {  // slot u <- column o of the walk
             const int c = dir ? x0 + CW - 1 - o : x0 + o;
             cc[u].load(rc, o < ncol ? cell64(c) * (uint32_t)sizeof(CT) : kOOB);
-            if constexpr (!ATOM) pb[u].load(rp, o < ncol ? cell64(c) * 2u : kOOB);
+            if constexpr (!ATOM) pb[u].template load<PAUX>(rp, o < ncol ? cell64(c) * 2u : kOOB);
         };
         auto issue = [&](int o0) {
 #pragma unroll
@@ -412,7 +416,7 @@ __global__ void __launch_bounds__(256) k_ew_patch(EwPatchArgs a)
                         P[q] = pk_add(pk_sub(pv_[q], Ln[0][q]), Ln[1][q]);
                     }
                 }
-                if constexpr (!ATOM) bstore_n<uint32_t, NPW>(rp, cell64(c) * 2u, P);
+                if constexpr (!ATOM) bstore_n<uint32_t, NPW, PAUX>(rp, cell64(c) * 2u, P);
 #pragma unroll
                 for (int q = 0; q < NPW; q++) {
                     Lq[0][q] = Ln[0][q];
@@ -445,8 +449,7 @@ __global__ void __launch_bounds__(256) k_ew_patch(EwPatchArgs a)
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     };
-    // phase A's open strips (walk never met), one bit per path position i >= 1
-    __shared__ uint64_t openm[4][kPatchMaxChunks];
+    // phase A's open strips (walk never met), one bit per path position i >= 1: openm[chunk]
     uint32_t nfix = 0, nopen = 0;  // walks (per line), open strips (wave-uniform)
     for (int dir = dir0; dir < dir1; dir++) {  // 0 = E (strips in x order), 1 = W (reverse)
         auto strip_of = [&](int i) { return dir ? nwg - 1 - i : i; };  // path position -> strip
@@ -493,7 +496,7 @@ __global__ void __launch_bounds__(256) k_ew_patch(EwPatchArgs a)
             }
             open = lines_or(open);
             nopen += (uint32_t)__builtin_popcountll(open);
-            if (lane == 0) openm[wave][ch] = open;
+            if (lane == 0) openm[ch] = open;
             if (open && first_open == nwg) first_open = i0 + __builtin_ctzll(open);
         }
         if (first_open < nwg && !EW_PATCH_NO_CARRY && D % 128 == 0 && EW_PATCH_B64 && !pil) {
@@ -510,7 +513,7 @@ __global__ void __launch_bounds__(256) k_ew_patch(EwPatchArgs a)
                     nfix += r != 2 && kl == 0;
                     if (r != 0) carry = false;
                 }
-                const bool open_i = ((openm[wave][(i - 1) / CHUNK] >> ((i - 1) % CHUNK)) & 1ull) != 0;
+                const bool open_i = ((openm[(i - 1) / CHUNK] >> ((i - 1) % CHUNK)) & 1ull) != 0;
                 if (!carry && open_i) {
                     load_state64(soff64(k, dir, 0), T);
                     carry = true;
@@ -534,7 +537,7 @@ __global__ void __launch_bounds__(256) k_ew_patch(EwPatchArgs a)
                     }
                     // an open strip's values (from e_{i-1}, or corrected to the true trajectory
                     // where that met them) end at c_k: the next strip needs c_k, not e_k
-                    const bool open_i = ((openm[wave][(i - 1) / CHUNK] >> ((i - 1) % CHUNK)) & 1ull) != 0;
+                    const bool open_i = ((openm[(i - 1) / CHUNK] >> ((i - 1) % CHUNK)) & 1ull) != 0;
                     if (!carry && open_i) {
                         load_state(soff(k, dir, 0), T);
                         carry = true;
@@ -549,6 +552,21 @@ __global__ void __launch_bounds__(256) k_ew_patch(EwPatchArgs a)
         if (lane == 0 && nfix) atomicAdd(a.fixes, (unsigned long long)nfix);
         if (lane == 0 && nopen) atomicAdd(a.fixes + 1, (unsigned long long)nopen);  // (the next counter)
     }
+}
+
+// grid ((H + 3) / 4, pairs) (ATOM: (2 H + 3) / 4), 256 threads: one wave per image row (ATOM: per
+// row and direction, E and W side by side)
+template <int VL, int NP, typename CT, bool ATOM = false>
+__global__ void __launch_bounds__(256) k_ew_patch(EwPatchArgs a)
+{
+    if (a.guard && __hip_atomic_load(a.guard, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) return;
+    const int wave = threadIdx.x >> 6;
+    const int yw = (int)blockIdx.x * 4 + wave;  // (wave-uniform)
+    const int y = ATOM ? yw >> 1 : yw;
+    const int dir0 = ATOM ? (yw & 1) : 0, dir1 = ATOM ? dir0 + 1 : 2;
+    if (y >= a.H) return;
+    __shared__ uint64_t openm[4][kPatchMaxChunks];
+    ew_patch_row<VL, NP, CT, ATOM>(a, blockIdx.y, y, dir0, dir1, openm[wave]);
 }
 
 // ---- row-band patch (BandPatchArgs): grid (nbx, nband - 1, pairs), 256 threads.

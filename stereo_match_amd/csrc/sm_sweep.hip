@@ -85,6 +85,16 @@ constexpr bool unit_built()
     else return true;
 }
 
+// patch waves of this unit's MODE 4 instance for the in-sweep E/W patch (host mode 5; 0: not built):
+// the wide u8 D = 128 instance, whose 16-lane lines are the patch pass's and whose patch role fits
+// the 128 VGPRs of a 15-wave workgroup (sm_sweep.hpp; DESIGN.md §4.4 addendum)
+template <int VL, int DPL, typename CT, int MODE>
+constexpr int unit_npw()
+{
+    return SWEEP_WIDE == 1 && MODE == 4 && sizeof(CT) == 1 && VL == 16 && VL * DPL == 128 ? SWEEP_NPW : 0;
+}
+
+template <bool PATCH = false>
 struct InfoF {
     int device;
     SweepInfo* out;
@@ -92,12 +102,13 @@ struct InfoF {
     hipError_t run()
     {
         constexpr int NCW = unit_ncw<VL * DPL, CT>();
-        if constexpr (!unit_built<VL, DPL, CT, MODE>()) {
+        constexpr int NPW = PATCH ? unit_npw<VL, DPL, CT, MODE>() : 0;
+        if constexpr (!unit_built<VL, DPL, CT, MODE>() || (PATCH && NPW == 0)) {
             return hipErrorInvalidValue;
         } else {
             using SG = SweepGeo<VL, DPL, NCW>;
-            constexpr int THREADS = sweep_threads<VL, DPL, NCW, MODE>();
-            auto kern = k_sweep<VL, DPL, CT, MODE, NCW>;
+            constexpr int THREADS = sweep_threads<VL, DPL, NCW, MODE, NPW>();
+            auto kern = k_sweep<VL, DPL, CT, MODE, NCW, NPW>;
             static int per_cu = -1;  // per instance (one device type per process)
             if (per_cu < 0) {
                 int nb = 0;
@@ -122,6 +133,7 @@ struct InfoF {
     }
 };
 
+template <bool PATCH = false>
 struct LaunchF {
     const SweepArgs* a;
     dim3 grid;
@@ -130,11 +142,12 @@ struct LaunchF {
     hipError_t run()
     {
         constexpr int NCW = unit_ncw<VL * DPL, CT>();
-        if constexpr (!unit_built<VL, DPL, CT, MODE>()) {
+        constexpr int NPW = PATCH ? unit_npw<VL, DPL, CT, MODE>() : 0;
+        if constexpr (!unit_built<VL, DPL, CT, MODE>() || (PATCH && NPW == 0)) {
             return hipErrorInvalidValue;
         } else {
-            hipLaunchKernelGGL((k_sweep<VL, DPL, CT, MODE, NCW>), grid, dim3(sweep_threads<VL, DPL, NCW, MODE>()), 0,
-                               stream, *a);
+            hipLaunchKernelGGL((k_sweep<VL, DPL, CT, MODE, NCW, NPW>), grid,
+                               dim3(sweep_threads<VL, DPL, NCW, MODE, NPW>()), 0, stream, *a);
             return hipGetLastError();
         }
     }
@@ -201,29 +214,45 @@ hipError_t sweep2(int D, int ct_bytes, int variant, bool info, int device, Sweep
 #if SWEEP_WIDE == 2
 hipError_t SW_CAT(sweep_info_lat_m, SWEEP_MODE)(int D, int ct_bytes, int device, SweepInfo* out)
 {
-    InfoF f{device, out};
+    InfoF<> f{device, out};
     return with_sweep(D, ct_bytes, f);
 }
 
 hipError_t SW_CAT(sweep_launch_lat_m, SWEEP_MODE)(int D, int ct_bytes, const SweepArgs& a, int npairs,
                                                   hipStream_t stream)
 {
-    LaunchF f{&a, a.xcd_per > 0 ? dim3(8 * a.xcd_per, 1) : dim3(a.nwg * (a.nband > 1 ? a.nband : 1), npairs), stream};
+    LaunchF<> f{&a, a.xcd_per > 0 ? dim3(8 * a.xcd_per, 1) : dim3(a.nwg * (a.nband > 1 ? a.nband : 1), npairs), stream};
     return with_sweep(D, ct_bytes, f);
 }
 #elif SWEEP_WIDE
 hipError_t SW_CAT(sweep_info_wide_m, SWEEP_MODE)(int D, int ct_bytes, int device, SweepInfo* out)
 {
-    InfoF f{device, out};
+    InfoF<> f{device, out};
     return with_sweep(D, ct_bytes, f);
 }
 
 hipError_t SW_CAT(sweep_launch_wide_m, SWEEP_MODE)(int D, int ct_bytes, const SweepArgs& a, int npairs,
                                                    hipStream_t stream)
 {
-    LaunchF f{&a, a.xcd_per > 0 ? dim3(8 * a.xcd_per, 1) : dim3(a.nwg * (a.nband > 1 ? a.nband : 1), npairs), stream};
+    LaunchF<> f{&a, a.xcd_per > 0 ? dim3(8 * a.xcd_per, 1) : dim3(a.nwg * (a.nband > 1 ? a.nband : 1), npairs), stream};
     return with_sweep(D, ct_bytes, f);
 }
+#if SWEEP_WIDE == 1 && SWEEP_MODE == 4
+// host mode 5: the MODE 4 instance with patch waves (unit_npw)
+hipError_t sweep_info_wide_m4p(int D, int ct_bytes, int device, SweepInfo* out)
+{
+    InfoF<true> f{device, out};
+    return with_sweep(D, ct_bytes, f);
+}
+
+hipError_t sweep_launch_wide_m4p(int D, int ct_bytes, const SweepArgs& a, int npairs, hipStream_t stream)
+{
+    if (!a.fixes || !a.st || a.flag_off == 0 || a.nband > 1 || a.pcw < 1 || a.pnwg < 1 || a.pnwg > patch_max_strips(D))
+        return hipErrorInvalidValue;
+    LaunchF<true> f{&a, a.xcd_per > 0 ? dim3(8 * a.xcd_per, 1) : dim3(a.nwg, npairs), stream};
+    return with_sweep(D, ct_bytes, f);
+}
+#endif
 #else
 hipError_t SW_CAT(sweep_info_m, SWEEP_MODE)(int D, int ct_bytes, int variant, int device, SweepInfo* out)
 {
@@ -233,7 +262,7 @@ hipError_t SW_CAT(sweep_info_m, SWEEP_MODE)(int D, int ct_bytes, int variant, in
 #else
     (void)variant;
 #endif
-    InfoF f{device, out};
+    InfoF<> f{device, out};
     return with_sweep(D, ct_bytes, f);
 }
 
@@ -248,7 +277,7 @@ hipError_t SW_CAT(sweep_launch_m, SWEEP_MODE)(int D, int ct_bytes, int variant, 
 #else
     (void)variant;
 #endif
-    LaunchF f{&a, a.xcd_per > 0 ? dim3(8 * a.xcd_per, 1) : dim3(a.nwg * (a.nband > 1 ? a.nband : 1), npairs), stream};
+    LaunchF<> f{&a, a.xcd_per > 0 ? dim3(8 * a.xcd_per, 1) : dim3(a.nwg * (a.nband > 1 ? a.nband : 1), npairs), stream};
     return with_sweep(D, ct_bytes, f);
 }
 #endif

@@ -43,6 +43,7 @@
 #include "sm_common.hpp"
 #include "sm_sweep_host.hpp"
 #include "sm_pk.hpp"
+#include "sm_ew.hpp"  // ew_patch_row: the E/W patch pass of one image row (the MODE 4 patch waves)
 
 #include <type_traits>
 
@@ -55,7 +56,9 @@ constexpr uint32_t SW_SPIN_LIMIT = 1u << 19;
 // SWEEP_STATS builds (tools/build_variant.sh): shader-clock cycles each wave spends in
 // the row / block synchronisation, summed per mode into SweepArgs::stats[8 * MODE + k]
 // (MODE 3's line waves, words 40..44: 40 own waves in wait_lines, 41 line waves in wait_cons,
-// 42 line waves in barriers, 43 line waves' lifetime, 44 line waves):
+// 42 line waves in barriers, 43 line waves' lifetime, 44 line waves; MODE 4 with patch waves,
+// words 45..47: 45 own waves waiting for patched rows in the sweep's first 40 rows, 46 in its
+// other rows, 47 the patch waves' lifetimes):
 // 0 poller in polls, 1 poller in barriers, 2 compute waves in wait_row, 3 compute waves
 // in block barriers, 4 compute waves' lifetime, 5 compute waves, 6 poller lifetime
 #if SWEEP_STATS
@@ -318,12 +321,38 @@ struct LineGeo {
         return largest_divisor_upto(G::CW / 2, VL == 8 ? 9 : sizeof(CT) == 1 ? SWEEP_LPF8 : SWEEP_LPF16);
     }
 };
-template <int VL, int DPL, int NCW_, int MODE>
+template <int VL, int DPL, int NCW_, int MODE, int NPW = 0>
 constexpr int sweep_threads()
 {
     using LG = LineGeo<VL, DPL, NCW_, MODE>;
-    return SweepGeo<VL, DPL, NCW_>::THREADS + 64 * (LG::NLW - (LG::HPOLL ? 1 : 0));  // (HPOLL: no poller)
+    return SweepGeo<VL, DPL, NCW_>::THREADS + 64 * (LG::NLW - (LG::HPOLL ? 1 : 0) + NPW);  // (HPOLL: no poller)
 }
+
+// ---- MODE 4 with NPW patch waves (DESIGN.md §4.4 addendum): the E/W patch pass of the 8-path
+// lines chain runs inside the up + WTA sweep instead of as a launch between the sweeps.  The pass
+// is bound by memory round trips on each row's serial check -> walk chain, not by work (7 M VALU
+// instructions against the sweep's 176 M), and the sweep needs row y's repaired partial only when
+// it reaches row y.  Row H - 1 - i of a pair (i: the order the sweep consumes the rows in) goes to
+// patch wave i % (nwg * NPW) of the pair's nwg workgroups; the wave runs ew_patch_row on it (the
+// whole row: check, phase A, phase B, E then W), drains its stores and publishes the row in
+// rowflag[pair][i] (SweepArgs::flag_off).  All inputs of a patch wave are MODE 3's outputs,
+// complete at the kernel boundary: the rows wait on nothing.  Each workgroup's last patch wave
+// also polls the flags in consumption order and advances the LDS counter patched_upto (rows 0 ..
+// patched_upto - 1 published); an own wave issues the partial load of row i only once patched_upto
+// > i (the linecnt / wait_lines pattern of MODE 3).  Every poll is bounded (timeout -> error word).
+// Visibility across workgroups (other XCDs' L2s, other CUs' L1s; MI355X guide §6 Guideline 16):
+// every repaired partial slice is stored sc1 (write-through), the storing wave waits vmcnt(0),
+// then its lane 0 stores the row's flag granule sc1; the polling wave reads the flags with sc1
+// loads and sets the LDS counter; EVERY partial load of this instance is an sc1 load (in place
+// of the other instances' nt), so no consumer reads the handed-off bytes through its L1.
+#ifndef SWEEP_PATCH_PRIO
+#define SWEEP_PATCH_PRIO 0  // issue priority of the patch waves (own waves: 3 on the row chain, else 1)
+#endif
+#ifndef SWEEP_PATCH_RC
+#define SWEEP_PATCH_RC 0  // columns a repaired segment loads together in the in-sweep walks (0: ew_patch_row's default)
+#endif
+// rows the polling wave waits for before its own first row (the sweep's first loads need them)
+constexpr int kPatchFirstRows = 16;
 
 // NP packed words of one lane <-> LDS (widest aligned chunks)
 template <int NP>
@@ -492,8 +521,8 @@ __device__ __forceinline__ void poll_granules(const gu64* src, bool need, uint32
     poll_set<N>(p, nd, tag, v, dead, err);
 }
 
-template <int VL, int DPL, typename CT, int MODE, int NCW_ = kNarrowNcw>
-__global__ void __launch_bounds__((sweep_threads<VL, DPL, NCW_, MODE>())) k_sweep(SweepArgs a)
+template <int VL, int DPL, typename CT, int MODE, int NCW_ = kNarrowNcw, int NPW = 0>
+__global__ void __launch_bounds__((sweep_threads<VL, DPL, NCW_, MODE, NPW>())) k_sweep(SweepArgs a)
 {
     using G = SweepGeo<VL, DPL, NCW_>;
     using LG = LineGeo<VL, DPL, NCW_, MODE, (int)sizeof(CT)>;
@@ -505,7 +534,9 @@ __global__ void __launch_bounds__((sweep_threads<VL, DPL, NCW_, MODE>())) k_swee
     constexpr bool HPOLL = LG::HPOLL;               // the halo waves poll their neighbours (no poller wave)
     static_assert(!LINES || LG::BUILT, "MODE 3 instance not built for this geometry");
     static_assert(MODE < 3 || (DPL % 2 == 0 && !SWEEP_U32), "MODES 3 / 4 run the packed row loops only");
-    constexpr int NTH = sweep_threads<VL, DPL, NCW_, MODE>();
+    constexpr int NTH = sweep_threads<VL, DPL, NCW_, MODE, NPW>();
+    static_assert(NPW == 0 || (MODE == 4 && HPOLL && sizeof(CT) == 1 && DPL % 2 == 0 && VL * DPL % 32 == 0 && VL == 16),
+                  "patch waves: the 8-path u8 up sweep on the patch pass's 16-lane lines, no poller wave");
     // the down sweep shares its SIMDs with the E/W kernel (8 paths): its waves take issue
     // priority, the E/W waves fill the cycles it leaves (SWEEP_PRIO 0 = default priority)
 #ifndef SWEEP_PRIO
@@ -528,7 +559,7 @@ __global__ void __launch_bounds__((sweep_threads<VL, DPL, NCW_, MODE>())) k_swee
     constexpr int NG = G::NG, SNG = G::SNG, PF = G::PF, HM = G::HM, HW = G::HW;
     constexpr int CB = DPL * (int)sizeof(CT);  // cost / E / W bytes per lane and cell
     constexpr bool IL = sweep_il<CT, DPL>();    // the lanes' words interleaved (SWEEP_IL)
-    constexpr int NPW = DPL / 2 > 0 ? DPL / 2 : 1;  // packed words per lane (even DPL)
+    constexpr int NPL = DPL / 2 > 0 ? DPL / 2 : 1;  // packed words per lane (even DPL)
     // [buf][A=+dx, B=-dx][col+1][lane slice of DPL, in word order (pk_slot)]
     __shared__ __attribute__((aligned(16))) uint16_t lv[2][2][COLS][D];
     __shared__ uint32_t lmin[2][2][COLS];
@@ -549,6 +580,10 @@ __global__ void __launch_bounds__((sweep_threads<VL, DPL, NCW_, MODE>())) k_swee
     __shared__ __attribute__((aligned(8))) uint32_t roff[LINES && LG::DSO ? LG::LR : 1][LINES && LG::DSO ? CW : 1][2];
     __shared__ uint32_t linecnt[LINES ? LG::NLW : 1], conscnt[NCW];
     __shared__ uint32_t pollcnt;  // NOBAR: blocks whose halo snapshot the poller has written
+    // patch waves: each wave's open-strip masks (ew_patch_row); rows (in consumption order) whose
+    // patch the polling wave has seen published
+    __shared__ uint64_t popen[NPW > 0 ? NPW : 1][NPW > 0 ? kPatchMaxChunks : 1];
+    __shared__ uint32_t patched_upto;
 
     // the workgroup's (pair, band, strip) item: blockIdx (x = band * nwg + strip, y = pair), or
     // the XCD-aware 1-D placement (SweepArgs::xcd_per)
@@ -581,8 +616,8 @@ __global__ void __launch_bounds__((sweep_threads<VL, DPL, NCW_, MODE>())) k_swee
         uint32_t v = 0;
         if (vguess) {
             const int q = (i / (D / 2)) % COLS, wi = i % (D / 2);  // word wi of the column: its two disparities
-            const int d0 = IL ? wi / NPW * DPL + pk_disp<NPW, IL>(wi % NPW, 0) : 2 * wi;
-            const int d1 = IL ? wi / NPW * DPL + pk_disp<NPW, IL>(wi % NPW, 1) : 2 * wi + 1;
+            const int d0 = IL ? wi / NPL * DPL + pk_disp<NPL, IL>(wi % NPL, 0) : 2 * wi;
+            const int d1 = IL ? wi / NPL * DPL + pk_disp<NPL, IL>(wi % NPL, 1) : 2 * wi + 1;
             if (in_domain_slot(q)) v = (uint32_t)(d0 % 5 + 3 * (q & 1)) | ((uint32_t)(d1 % 5 + 3 * (q & 1)) << 16);
         }
         reinterpret_cast<uint32_t*>(&lv[0][0][0][0])[i] = v;
@@ -592,7 +627,7 @@ __global__ void __launch_bounds__((sweep_threads<VL, DPL, NCW_, MODE>())) k_swee
         (&lmin[0][0][0])[i] = vguess && in_domain_slot(q) ? (uint32_t)(3 * (q & 1)) * 0x10001u : 0u;
     }
     for (int i = threadIdx.x; i < NCW; i += NTH) rowcnt[i] = conscnt[i] = 0;
-    if (threadIdx.x == 0) pollcnt = 0;
+    if (threadIdx.x == 0) pollcnt = patched_upto = 0;
 
     if constexpr (LINES)
         for (int i = threadIdx.x; i < LG::NLW; i += NTH) linecnt[i] = 0;
@@ -985,6 +1020,90 @@ __global__ void __launch_bounds__((sweep_threads<VL, DPL, NCW_, MODE>())) k_swee
         }
     }
 
+    if constexpr (NPW > 0) {
+        if (wave >= NCW) {
+            // ---- patch waves (MODE 4 with NPW > 0, see above): wave pw of strip wg is patch wave
+            // pw * nwg + wg of the pair, so the polling waves (pw = NPW - 1) own the latest rows
+            const int pw = __builtin_amdgcn_readfirstlane(wave) - NCW;
+            const bool poller = pw == NPW - 1;
+            __builtin_amdgcn_s_setprio(SWEEP_PATCH_PRIO);
+            SW_T0(pst_life);
+            EwPatchArgs pa{};
+            pa.cost = a.cost;
+            pa.cost_pair = a.cost_pair;
+            pa.part = a.part;
+            pa.part_pair = a.part_pair;
+            pa.st = a.st;
+            pa.st_pair = a.st_pair;
+            pa.H = H;
+            pa.W1 = W1;
+            pa.nwg = a.pnwg;  // MODE 3's strips
+            pa.cw = a.pcw;
+            pa.P1 = a.P1;
+            pa.P2 = a.P2;
+            pa.fixes = a.fixes;
+            pa.part_il = a.part_il;
+            const int nid = a.nwg * NPW, id = pw * a.nwg + wg;
+            gu64* const flags = (gu64*)(hopp + a.flag_off);
+            const uint32_t ftag = tag0 | 0xFFFFu;  // (a snapshot's tag ends in its block number, far below)
+            // MODE 3 gave up on the group (the guarded fallback recomputes it): nothing to patch,
+            // the rows are still published
+            const bool gaveup = __hip_atomic_load(a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u;
+            uint32_t upto = 0;  // wave-uniform: rows 0 .. upto - 1 seen published
+            bool pdead = (a.dbg & 1) != 0;
+            auto set_upto = [&](uint32_t v) {
+                __hip_atomic_store(&patched_upto, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            };
+            // the polling wave: the flags from `upto` on, 64 per pass, up to the first one not yet
+            // published; block: until `target` rows are published (bounded), else one look
+            auto advance = [&](uint32_t target, bool block) {
+                if (!poller) return;
+                for (uint32_t spins = 0; upto < target && !pdead;) {
+                    const uint32_t idx = upto + (uint32_t)lane;
+                    const unsigned long long x =
+                        __hip_atomic_load(flags + min(idx, (uint32_t)(H - 1)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    const bool ok = idx >= (uint32_t)H || (uint32_t)(x >> 32) == ftag;
+                    const unsigned long long nb = ~__ballot(ok);
+                    const uint32_t nset = nb ? (uint32_t)__builtin_ctzll(nb) : 64u;
+                    if (nset) {
+                        upto = min(upto + nset, (uint32_t)H);
+                        set_upto(upto);
+                        spins = 0;
+                        if (nset == 64u) continue;
+                    }
+                    if (!block) return;
+                    if (nset == 0u) {
+                        if (++spins >= SW_SPIN_LIMIT) {  // never expected: report, the guarded fallback recomputes
+                            if (lane == 0) atomicOr(a.err, 1u);
+                            pdead = true;
+                            break;
+                        }
+                        __builtin_amdgcn_s_sleep(2);
+                    }
+                }
+                if (pdead) set_upto((uint32_t)H);  // (results void: let the own waves finish)
+            };
+            // the sweep's first rows, all owned by waves that wait on nothing (pw < NPW - 1)
+            advance((uint32_t)min(H, min(kPatchFirstRows, (NPW - 1) * a.nwg)), true);
+            for (int i = id; i < H; i += nid) {
+                if (!gaveup)
+                    ew_patch_row<VL, DPL / 2, CT, false, true, SWEEP_PATCH_RC>(pa, (size_t)pair, H - 1 - i, 0, 2, popen[pw]);
+                // the row's write-through stores have left the wave, then its flag (sc1 store)
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                if (lane == 0)
+                    __hip_atomic_store(flags + i, (unsigned long long)ftag << 32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                advance((uint32_t)H, false);
+            }
+            advance((uint32_t)H, true);
+#if SWEEP_STATS
+            if (a.stats && lane == 0) {
+                atomicAdd(a.stats + 47, (unsigned long long)(__builtin_readcyclecounter() - pst_life));
+            }
+#endif
+            return;
+        }
+    }
+
     // ---- compute waves
     const int kl = lane / VL, g = lane % VL;
     // column slot among the compute waves (halo waves: of their first column set)
@@ -1006,6 +1125,7 @@ __global__ void __launch_bounds__((sweep_threads<VL, DPL, NCW_, MODE>())) k_swee
         __hip_atomic_store(&rowcnt[wave], (uint32_t)(s + 1), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
     };
     [[maybe_unused]] uint64_t st_wait = 0, st_bbar = 0;
+    [[maybe_unused]] uint64_t st_pw0 = 0, st_pw1 = 0;  // own waves waiting for patched rows: steps < 40, the rest
     SW_T0(st_clife);
     auto wait_row_spin = [&](int s) {
         for (uint32_t spins = 0;; spins++) {
@@ -1178,8 +1298,37 @@ __global__ void __launch_bounds__((sweep_threads<VL, DPL, NCW_, MODE>())) k_swee
                     re_[k].template load<SWEEP_STREAM_AUX>(re, boff(en, sizeof(CT)));
                     rw_[k].template load<SWEEP_STREAM_AUX>(rw, boff(en, sizeof(CT)));
                 }
-                if constexpr (OWN && PARTR) rp_[k].template load<SWEEP_STREAM_AUX>(rp, boff(s < nrow ? cell(yy) : NONE, 2));
+                // (patch waves: rows other workgroups repair inside the launch, every load of them sc1)
+                if constexpr (OWN && PARTR)
+                    rp_[k].template load<(NPW > 0 ? 16 : SWEEP_STREAM_AUX)>(rp, boff(s < nrow ? cell(yy) : NONE, 2));
             };
+            // patch waves: step s's partial row is published (rows 0 .. patched_upto - 1 are); the
+            // counter only grows, so the last value seen answers most calls without an LDS read
+            [[maybe_unused]] uint32_t pseen = 0;
+            auto wait_patched = [&](int s) {
+                if constexpr (OWN && NPW > 0) {
+                    const uint32_t need = (uint32_t)s + 1u;
+                    if (pseen >= need) return;
+                    SW_T0(tp);
+                    for (uint32_t spins = 0;; spins++) {
+                        pseen = __builtin_amdgcn_readfirstlane(
+                            __hip_atomic_load(&patched_upto, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+                        if (pseen >= need) break;
+                        if (spins >= SW_SPIN_LIMIT) {  // never expected: report, the guarded fallback recomputes
+                            if (lane == 0) atomicOr(a.err, 1u);
+                            pseen = 0xFFFFFFFFu;
+                            break;
+                        }
+                        __builtin_amdgcn_s_sleep(1);
+                    }
+                    if (s < 40) SW_ACC(st_pw0, tp);
+                    else SW_ACC(st_pw1, tp);
+                    asm volatile("" ::: "memory");  // the row's loads stay behind the counter's read
+                } else {
+                    (void)s;
+                }
+            };
+            if (nrow > 0) wait_patched(min(PF, nrow) - 1);
 #pragma unroll
             for (int k = 0; k < PF; k++) issue_r(k, k);
             uint32_t LVp[NP];
@@ -1258,6 +1407,7 @@ __global__ void __launch_bounds__((sweep_threads<VL, DPL, NCW_, MODE>())) k_swee
                         if constexpr (OWN && EWIN) asm volatile("" : "+v"(Ein[i]), "+v"(Win[i])::"memory");
                         if constexpr (OWN && PARTR) asm volatile("" : "+v"(Pin[i])::"memory");
                     }
+                    if (s + PF < nrow) wait_patched(s + PF);
                     issue_r(k, s + PF);
                     if (ROWSYNC && (j > 0 || NOBAR)) wait_row(s);
                     // diagonal predecessors: column c-1 (A) and c+1 (B) of the previous row
@@ -1655,6 +1805,10 @@ __global__ void __launch_bounds__((sweep_threads<VL, DPL, NCW_, MODE>())) k_swee
                 atomicAdd(a.stats + 8 * MODE + 4, (unsigned long long)(__builtin_readcyclecounter() - st_clife));
                 atomicAdd(a.stats + 8 * MODE + 5, 1ull);
                 if (LINES) atomicAdd(a.stats + 40, (unsigned long long)st_wl);
+                if (NPW > 0 && OWN) {  // words 45 / 46 (47: the patch waves' lifetimes)
+                    atomicAdd(a.stats + 45, (unsigned long long)st_pw0);
+                    atomicAdd(a.stats + 46, (unsigned long long)st_pw1);
+                }
             }
 #endif
         };

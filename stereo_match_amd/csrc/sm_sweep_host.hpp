@@ -11,6 +11,7 @@ namespace smk {
 //       3 = down sweep + in-kernel E/W lines (speculative strip segments)
 //           writing the u16 partial S + SE + SW + E + W and the segments' boundary states
 //       4 = up sweep + partial + WTA (8 paths, second pass after MODE 3: no E/W volumes)
+//       (host mode 5 = the MODE 4 kernel with patch waves: the E/W patch pass inside the sweep)
 #ifndef SWEEP_STATS
 #define SWEEP_STATS 0  // sm_sweep.hpp: wait-cycle counters (variant builds)
 #endif
@@ -77,8 +78,22 @@ struct SweepArgs {
     // 8-path lines chain MODE 3 -> k_ew_patch -> MODE 4 where the patch pass runs lines of the
     // sweeps' geometry (EwPatchArgs::part_il); every other reader of a partial gets it d-contiguous
     int part_il;
+    // MODE 4 with patch waves (k_sweep's NPW > 0; host mode 5): the E/W patch pass
+    // runs inside this launch.  fixes: k_ew_patch's counters (EwPatchArgs::fixes); flag_off: granule
+    // offset in a pair's hop record of rowflag[H], one {0, epoch << 16 | 0xFFFF} granule per image
+    // row in the order the sweep consumes them (index i = row H - 1 - i), written when the row's
+    // patch is complete.  The patch reads st (MODE 3's boundary states) and the give-up word err.
+    // pnwg, pcw: strips per pair and strip width of the MODE 3 launch that wrote st (its own
+    // instance: the strips the patch pass checks need not be this sweep's).
+    unsigned long long* fixes;
+    size_t flag_off;
+    int pnwg, pcw;
 };
 
+// patch waves per workgroup of the up + WTA sweep's in-sweep patch instance (host mode 5)
+#ifndef SWEEP_NPW
+#define SWEEP_NPW 4
+#endif
 
 struct SweepInfo {
     int cw;             // own columns per workgroup (strip width)
@@ -109,6 +124,8 @@ hipError_t sweep_info_wide_m1(int D, int ct_bytes, int device, SweepInfo* out);
 hipError_t sweep_info_wide_m2(int D, int ct_bytes, int device, SweepInfo* out);
 hipError_t sweep_info_wide_m3(int D, int ct_bytes, int device, SweepInfo* out);
 hipError_t sweep_info_wide_m4(int D, int ct_bytes, int device, SweepInfo* out);
+// host mode 5: the MODE 4 kernel with SWEEP_NPW patch waves (wide strips, u8 costs, D = 128)
+hipError_t sweep_info_wide_m4p(int D, int ct_bytes, int device, SweepInfo* out);
 hipError_t sweep_info_lat_m0(int D, int ct_bytes, int device, SweepInfo* out);
 hipError_t sweep_info_lat_m1(int D, int ct_bytes, int device, SweepInfo* out);
 hipError_t sweep_info_lat_m2(int D, int ct_bytes, int device, SweepInfo* out);
@@ -130,6 +147,7 @@ hipError_t sweep_launch_wide_m1(int D, int ct_bytes, const SweepArgs& a, int npa
 hipError_t sweep_launch_wide_m2(int D, int ct_bytes, const SweepArgs& a, int npairs, hipStream_t stream);
 hipError_t sweep_launch_wide_m3(int D, int ct_bytes, const SweepArgs& a, int npairs, hipStream_t stream);
 hipError_t sweep_launch_wide_m4(int D, int ct_bytes, const SweepArgs& a, int npairs, hipStream_t stream);
+hipError_t sweep_launch_wide_m4p(int D, int ct_bytes, const SweepArgs& a, int npairs, hipStream_t stream);
 
 inline hipError_t sweep_info(int D, int ct_bytes, int mode, int variant, int device, SweepInfo* out)
 {
@@ -140,6 +158,7 @@ inline hipError_t sweep_info(int D, int ct_bytes, int mode, int variant, int dev
     static const InfoW wide[5] = {sweep_info_wide_m0, sweep_info_wide_m1, sweep_info_wide_m2, sweep_info_wide_m3,
                                   sweep_info_wide_m4};
     static const InfoV narrow[5] = {sweep_info_m0, sweep_info_m1, sweep_info_m2, sweep_info_m3, sweep_info_m4};
+    if (mode == 5) return variant == 0 ? sweep_info_wide_m4p(D, ct_bytes, device, out) : hipErrorInvalidValue;
     if (mode < 0 || mode > 4) return hipErrorInvalidValue;
     if (variant == 2) return lat[mode](D, ct_bytes, device, out);  // latency instances (kLatNcw compute waves)
     if (variant == 0) {
@@ -159,6 +178,7 @@ inline hipError_t sweep_launch(int D, int ct_bytes, int mode, int impl, const Sw
                                     sweep_launch_wide_m3, sweep_launch_wide_m4};
     static const LaunchV narrow[5] = {sweep_launch_m0, sweep_launch_m1, sweep_launch_m2, sweep_launch_m3,
                                       sweep_launch_m4};
+    if (mode == 5) return impl == 1 ? sweep_launch_wide_m4p(D, ct_bytes, a, npairs, stream) : hipErrorInvalidValue;
     if (mode < 0 || mode > 4) return hipErrorInvalidValue;
     if (impl == 2) return lat[mode](D, ct_bytes, a, npairs, stream);
     if (impl == 1) return wide[mode](D, ct_bytes, a, npairs, stream);

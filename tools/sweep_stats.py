@@ -20,6 +20,8 @@ L = torch.tensor(np.stack([a for a, _ in pairs]), device="cuda")
 R = torch.tensor(np.stack([b for _, b in pairs]), device="cuda")
 out = torch.empty((n, H, W), dtype=torch.int16, device="cuda")
 eng = _lib.Engine(0)
+if len(sys.argv) > 2:  # SM_TUNE_EW_PATCH (1: the patch pass inside the up sweep, -1: its own launch)
+    eng.set_tuning(eng.TUNE_EW_PATCH, int(sys.argv[2]))
 sp = synthetic.to_sm_params(p)
 for _ in range(3):
     eng.compute_batch_device(L.data_ptr(), R.data_ptr(), n, H * W, H, W, W, sp, out.data_ptr())
@@ -39,6 +41,11 @@ if ln[4]:  # MODE 3's line waves (words 40..44)
     own_life = st[3][4]
     print(f"mode 3 lines: {int(ln[4])} line waves, life {ln[3] / ln[4] / reps:.0f} cyc/launch; wait_cons "
           f"{ln[1] / ln[3]:.3f}, barriers {ln[2] / ln[3]:.3f}; own waves in wait_lines {ln[0] / max(own_life, 1):.3f}")
+if ln[5] or ln[6] or ln[7]:  # MODE 4's patch waves (words 45..47; SM_TUNE_EW_PATCH 1)
+    own = max(st[4][5] - 2 * st[4][5] / 11, 1)  # own waves: 9 of a strip's 11 compute waves
+    print(f"mode 4 patch waves: own waves waiting for patched rows, cyc/wave/launch: first 40 rows "
+          f"{ln[5] / own / reps:.0f}, other rows {ln[6] / own / reps:.0f} (of life {st[4][4] / max(st[4][5], 1) / reps:.0f}); "
+          f"patch waves' lives {ln[7] / reps:.0f} cyc/launch in total")
 for m in range(5):
     s = st[m]
     if s[5] == 0:
