@@ -374,6 +374,67 @@ int sm_cloud_ply(sm_ctx* ctx, const void* disp, int disp_type, const uint8_t* bg
                  const double* Q, const sm_cloud_params* p, size_t capacity_bytes, char* out, int64_t* count,
                  uint64_t* nbytes);
 
+/* ---- PNG output: cv2.imwrite(".png") of the reference's scripts
+ * (disparity_calculation.py:247-291, rectified_img_cal.py:316-319, disparity_test.py:114-115) and
+ * the KITTI disparity format, encoded on the device.
+ *
+ * The file: signature, IHDR, one IDAT chunk per SM_PNG_SEG bytes of the filtered stream, IEND; no
+ * interlace, no ancillary chunks.  Pixels: uint8 gray (colour type 0), uint8 x 3 (colour type 2;
+ * the memory order is BGR and the file's RGB as with cv2.imwrite, unless keep_channel_order),
+ * uint16 gray (big-endian samples).  A disparity map (int16 x16 or float32) is converted while
+ * it is read:
+ *   SM_PNG_DISP_KITTI      uint16 = disparity * 256: int16 d < 0 -> 0, else min(65535, d << 4) (exact up
+ *                          to d = 4095, disparity 255.9375); float32 non-finite or <= 0 -> 0, else
+ *                          min(65535, rint(d * 256)) (float32, ties to even)
+ *   SM_PNG_DISP_LINEAR_U8  int16 maps only: uint8 v = clamp(((d - lo) * 510 + (hi - lo)) / (2 * (hi - lo)),
+ *                          0, 255) in 64-bit integers (round half up); hi == lo gives 0 everywhere;
+ *                          without has_bounds lo / hi are the map's own minimum and maximum
+ *                          (show_disparity's normalize(NORM_MINMAX), plot_functions.py:99-100; the
+ *                          rounding is this package's contract, OpenCV's is not pinned).
+ * Filter: -1 picks per row the type whose filtered bytes, taken as signed magnitudes
+ * (b < 128 ? b : 256 - b), sum to the least, ties to the lowest type (libpng's heuristic);
+ * 0..4 fixes the type.  Deflate: every segment on its own (runs as matches at distance 1 +
+ * literals, one dynamic Huffman block, or a stored block when that is smaller); a segment that
+ * is not the last is closed on a byte boundary by an empty stored block.  The first chunk
+ * begins with the zlib header 78 01, the last ends with the stream's Adler-32. */
+#define SM_PNG_SEG 32768
+#define SM_PNG_SRC_U8 0
+#define SM_PNG_SRC_U16 1
+#define SM_PNG_SRC_DISP_I16 2
+#define SM_PNG_SRC_DISP_F32 3
+#define SM_PNG_DISP_KITTI 0
+#define SM_PNG_DISP_LINEAR_U8 1
+typedef struct sm_png_params {
+    int src_kind;           /* SM_PNG_SRC_* */
+    int channels;           /* 1, or 3 (SM_PNG_SRC_U8 only) */
+    int keep_channel_order; /* 3 channels: 0 swaps BGR -> RGB, 1 writes the memory order */
+    int filter;             /* -1 adaptive, 0..4 a fixed type */
+    int disp_mode;          /* SM_PNG_DISP_* (disparity sources) */
+    int has_bounds;         /* SM_PNG_DISP_LINEAR_U8: lo / hi given (else the map's min / max) */
+    int lo, hi;             /* in the map's units (disparity x 16) */
+} sm_png_params;
+
+/* The largest file an image of this shape can make (every segment stored); 0 for a shape that
+ * is not encoded.  channels / depth are the file's (1 or 3; 8 or 16). */
+size_t sm_png_bound(int H, int W, int channels, int depth);
+/* nimg images of one shape (image i at d_img + i*img_stride_bytes, rows row_stride_bytes apart):
+ * file i at d_out + i*capacity_bytes, its size in d_nbytes[i]; a byte that does not fit the
+ * capacity is left out (sm_png_bound always fits).  d_out NULL with capacity 0: sizes only.
+ * SM_E_UNSUPPORTED: (W*bpp + 1)*H >= 2^31 (bpp: bytes per pixel of the file).  Rows of up to
+ * 12288 bytes are staged in LDS; wider ones are converted where they are used.
+ * Asynchronous. */
+int sm_png_encode_batch_device(sm_ctx* ctx, const void* d_img, size_t img_stride_bytes, size_t row_stride_bytes,
+                               int nimg, int H, int W, const sm_png_params* p, size_t capacity_bytes, uint8_t* d_out,
+                               uint64_t* d_nbytes);
+/* One image on host pointers; *nbytes is always set; SM_E_ARG with nothing copied out when the
+ * capacity is too small.  Synchronous. */
+int sm_png_encode(sm_ctx* ctx, const void* img, size_t row_stride_bytes, int H, int W, const sm_png_params* p,
+                  size_t capacity_bytes, uint8_t* out, uint64_t* nbytes);
+/* The same file by the same functions on the CPU.  Needs no context and no device (one thread, one
+ * stream). */
+int sm_png_encode_host(const void* img, size_t row_stride_bytes, int H, int W, const sm_png_params* p,
+                       size_t capacity_bytes, uint8_t* out, uint64_t* nbytes);
+
 /* ---- StereoBM (the reference's method="BM" branch,
  * stereo_vision/stereo_vision.py:164-166: cv2.StereoBM_create(numDisparities,
  * blockSize)).  Fields follow cv::StereoBM's setters. */

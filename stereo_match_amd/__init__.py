@@ -16,6 +16,9 @@ Public surface (mirrors the reference / OpenCV names the reference uses):
   ``cv2.pyrDown`` in front of ``try_try.py``'s matcher (``:56-57``)
 * :func:`extract_point_cloud`, :func:`format_ply`, :func:`write_point_cloud` — the masked point
   cloud and its ASCII PLY file, the tail of every script (``disparity_calculation.py:302-320``)
+* :func:`imwrite`, :func:`imencode_png`, :func:`imencode_png_batch`, :func:`imencode_png_host`,
+  :func:`write_disparity_png`, :func:`encode_disparity_png` — PNG files (``cv2.imwrite``,
+  ``disparity_calculation.py:247-291``) and the KITTI 16-bit disparity format, encoded on the device
 
 All compute runs in ``libstereo_match_amd.so`` (HIP, gfx950) through the
 C-ABI in ``include/stereo_match_amd.h``; there is no CPU fallback.
@@ -31,6 +34,8 @@ from .rectify import (CALIB_ZERO_DISPARITY, COLOR_BGR2GRAY, CV_32FC1, INTER_LINE
                       initUndistortRectifyMap, rectify_opencv, remap, stereoRectify)
 from .denoise import fastNlMeansDenoising
 from .pointcloud import extract_point_cloud, format_ply, write_point_cloud
+from .png import (encode_disparity_png, imencode_png, imencode_png_batch, imencode_png_host, imwrite,
+                  write_disparity_png)
 from . import filters
 from .filters import gaussian_filter, image_measure, pyrDown
 
@@ -42,6 +47,8 @@ __all__ = [
     "stereoRectify", "initUndistortRectifyMap", "remap", "cvtColor", "rectify_opencv", "StereoRectifier",
     "CALIB_ZERO_DISPARITY", "CV_32FC1", "INTER_LINEAR", "COLOR_BGR2GRAY", "fastNlMeansDenoising",
     "extract_point_cloud", "format_ply", "write_point_cloud",
+    "imwrite", "imencode_png", "imencode_png_batch", "imencode_png_host", "write_disparity_png",
+    "encode_disparity_png",
     "filters", "gaussian_filter", "image_measure", "pyrDown",
 ]
 __version__ = "0.1.0"

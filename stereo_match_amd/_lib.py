@@ -72,6 +72,17 @@ class SmCloudParams(ctypes.Structure):
 
 
 SM_CLOUD_LO_NONE, SM_CLOUD_LO_VALUE, SM_CLOUD_LO_MIN = 0, 1, 2
+
+
+class SmPngParams(ctypes.Structure):
+    """Mirror of ``struct sm_png_params`` (PNG source kind, filter and disparity conversion)."""
+    _fields_ = [(n, ctypes.c_int) for n in (
+        "src_kind", "channels", "keep_channel_order", "filter", "disp_mode", "has_bounds", "lo", "hi")]
+
+
+SM_PNG_SEG = 32768
+SM_PNG_SRC_U8, SM_PNG_SRC_U16, SM_PNG_SRC_DISP_I16, SM_PNG_SRC_DISP_F32 = 0, 1, 2, 3
+SM_PNG_DISP_KITTI, SM_PNG_DISP_LINEAR_U8 = 0, 1
 PLY_MAX_ROW = 157  # bytes of the longest row '%f %f %f %d %d %d ' + newline
 
 ABI_VERSION = 3  # include/stereo_match_amd.h SM_ABI_VERSION this binding is written against
@@ -169,6 +180,14 @@ _SIGS = {
     "sm_cloud_ply": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int,
                                 _c.c_void_p, _c.POINTER(SmCloudParams), _c.c_size_t, _c.c_void_p,
                                 _c.POINTER(_c.c_int64), _c.POINTER(_c.c_uint64)]),
+    "sm_png_bound": (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int, _c.c_int]),
+    "sm_png_encode_batch_device": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_size_t, _c.c_int, _c.c_int,
+                                              _c.c_int, _c.POINTER(SmPngParams), _c.c_size_t, _c.c_void_p,
+                                              _c.c_void_p]),
+    "sm_png_encode": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_int, _c.c_int, _c.POINTER(SmPngParams),
+                                 _c.c_size_t, _c.c_void_p, _c.POINTER(_c.c_uint64)]),
+    "sm_png_encode_host": (_c.c_int, [_c.c_void_p, _c.c_size_t, _c.c_int, _c.c_int, _c.POINTER(SmPngParams),
+                                      _c.c_size_t, _c.c_void_p, _c.POINTER(_c.c_uint64)]),
     "sm_bm_default_params": (_c.c_int, [_c.c_int, _c.c_int, _c.POINTER(SmBmParams)]),
     "sm_bm_right_matcher_params": (_c.c_int, [_c.POINTER(SmBmParams), _c.POINTER(SmBmParams)]),
     "sm_bm_compute": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int,
@@ -228,6 +247,32 @@ def ply_format_host(verts: np.ndarray, colors: np.ndarray, capacity: int = None)
     out = np.empty(int(capacity), np.uint8)
     rc = lib.sm_ply_format_host(v.ctypes.data, c.ctypes.data, n, out.size, out.ctypes.data if out.size else None,
                                 ctypes.byref(nb))
+    if rc != SM_OK:
+        _raise(rc, None)
+    return out[:nb.value]
+
+
+def png_file_geometry(prm: "SmPngParams"):
+    """(channels, depth) of the file an image with these parameters makes."""
+    if prm.src_kind == SM_PNG_SRC_U8:
+        return prm.channels, 8
+    if prm.src_kind == SM_PNG_SRC_U16:
+        return 1, 16
+    return 1, (8 if prm.disp_mode == SM_PNG_DISP_LINEAR_U8 else 16)
+
+
+def png_encode_host(img: np.ndarray, prm: "SmPngParams", capacity: int = None) -> np.ndarray:
+    """sm_png_encode_host: the PNG file of a 2-D (or [H, W, 3]) array as a uint8 array, encoded on
+    the CPU by the functions the GPU kernels run.  Needs no context and no device.  ``capacity``
+    (default: sm_png_bound) bounds the output buffer; a file that does not fit is a ValueError."""
+    lib = load()
+    H, W = img.shape[:2]
+    if capacity is None:
+        capacity = lib.sm_png_bound(H, W, *png_file_geometry(prm))
+    out = np.empty(int(capacity), np.uint8)
+    nb = ctypes.c_uint64()
+    rc = lib.sm_png_encode_host(img.ctypes.data, img.strides[0] if img.size else 0, H, W, ctypes.byref(prm), out.size,
+                                out.ctypes.data if out.size else None, ctypes.byref(nb))
     if rc != SM_OK:
         _raise(rc, None)
     return out[:nb.value]
@@ -619,6 +664,22 @@ class Engine:
         return out[:nb.value], n.value
 
     # -- fastNlMeansDenoising -------------------------------------------------------------
+    def png_encode(self, img: np.ndarray, prm: "SmPngParams") -> np.ndarray:
+        """sm_png_encode: the PNG file of a host array as a uint8 array (encoded on the device)."""
+        H, W = img.shape[:2]
+        out = np.empty(self._lib.sm_png_bound(H, W, *png_file_geometry(prm)), np.uint8)
+        nb = ctypes.c_uint64()
+        self._check(self._lib.sm_png_encode(self.ctx, img.ctypes.data, img.strides[0] if img.size else 0, H, W,
+                                            ctypes.byref(prm), out.size, out.ctypes.data if out.size else None,
+                                            ctypes.byref(nb)))
+        return out[:nb.value]
+
+    def png_encode_batch_device(self, d_img: int, img_stride: int, row_stride: int, nimg: int, H: int, W: int,
+                                prm: "SmPngParams", capacity_bytes: int, d_out: int, d_nbytes: int):
+        self._check(self._lib.sm_png_encode_batch_device(
+            self.ctx, ctypes.c_void_p(d_img), img_stride, row_stride, nimg, H, W, ctypes.byref(prm), capacity_bytes,
+            ctypes.c_void_p(d_out or None), ctypes.c_void_p(d_nbytes or None)))
+
     def nlm_denoise(self, src: np.ndarray, h: float, template_window: int, search_window: int,
                     dst: np.ndarray = None) -> np.ndarray:
         """fastNlMeansDenoising of a uint8 [H, W] image (any row stride, pixels contiguous);

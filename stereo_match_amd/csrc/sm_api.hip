@@ -36,6 +36,7 @@
 #include "sm_nlm.hpp"
 #include "sm_filter.hpp"
 #include "sm_cloud.hpp"
+#include "sm_png.hpp"
 #include "sm_bm.hpp"
 #include "sm_wide.hpp"
 #include "sm_sweep_host.hpp"
@@ -152,6 +153,9 @@ struct sm_ctx {
     // point clouds (sm_cloud.hpp): block totals and their scans of the extraction (cl_) and the
     // PLY formatter (ply_); vertices, colours and the PLY body of the host and fused entry points
     DevBuf cl_tot, cl_off, ply_tot, ply_off, cl_verts, cl_colors, cl_out;
+    // PNG output (sm_png.hpp): the filtered streams, the segments' data and records, the chunk
+    // offsets, per-image records, min / max keys; image, files and sizes of the host entry point
+    DevBuf png_stream, png_slots, png_seg, png_off, png_img, png_range, png_in, png_out, png_nb;
     DevBuf flt_a;  // image_measure: the first Gaussian's result, [img][H][W] float64
     DevBuf wls_num, wls_den, wls_inter, wls_w, wls_disp[2], wls_out;  // WLS scratch
     DevBuf wls_R, wls_IT;         // WLS: Thomas pivots / elimination factors of every pass
@@ -2523,7 +2527,9 @@ void sm_destroy(sm_ctx* ctx)
                       &ctx->bm_cost, &ctx->hop,     &ctx->sweep_err, &ctx->wls_R,      &ctx->wls_IT,
                       &ctx->volwin,  &ctx->rm_src,  &ctx->rm_mapx,   &ctx->rm_mapy,     &ctx->rm_dst,
                       &ctx->rm_gray, &ctx->nlm_tab, &ctx->cl_tot,    &ctx->cl_off,      &ctx->ply_tot,
-                      &ctx->ply_off, &ctx->cl_verts, &ctx->cl_colors, &ctx->cl_out,      &ctx->flt_a};
+                      &ctx->ply_off, &ctx->cl_verts, &ctx->cl_colors, &ctx->cl_out,      &ctx->flt_a,
+                      &ctx->png_stream, &ctx->png_slots, &ctx->png_seg, &ctx->png_off, &ctx->png_img,
+                      &ctx->png_range, &ctx->png_in, &ctx->png_out, &ctx->png_nb};
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (auto& bs : ctx->set) {
@@ -3880,6 +3886,177 @@ int sm_ply_format_host(const float* verts, const uint8_t* colors, size_t n, size
         return fail(nullptr, SM_E_ARG, "ply: the body is %llu bytes, the capacity is %zu", (unsigned long long)at[nt],
                     capacity_bytes);
     run(true);
+    return SM_OK;
+}
+
+// ---- PNG output (sm_png.hpp)
+namespace {
+
+// the checks and the geometry of all three entry points (ctx NULL: the CPU twin)
+int png_setup(sm_ctx* ctx, const void* img, size_t img_stride, size_t row_stride, int nimg, int H, int W,
+              const sm_png_params* p, smk::PngArgs& a)
+{
+    if (!img || !p) return fail(ctx, SM_E_ARG, "png: a required pointer is NULL");
+    if (H <= 0 || W <= 0) return fail(ctx, SM_E_ARG, "png: empty image (%dx%d)", W, H);
+    if (nimg < 1 || nimg > 65535) return fail(ctx, SM_E_ARG, "png: nimg %d", nimg);
+    if (p->src_kind < SM_PNG_SRC_U8 || p->src_kind > SM_PNG_SRC_DISP_F32)
+        return fail(ctx, SM_E_ARG, "png: src_kind %d unknown", p->src_kind);
+    const bool disp = p->src_kind >= SM_PNG_SRC_DISP_I16;
+    if (p->src_kind == SM_PNG_SRC_U8 ? (p->channels != 1 && p->channels != 3) : p->channels != 1)
+        return fail(ctx, SM_E_ARG, "png: %d channels (uint8: 1 or 3; uint16 and disparity maps: 1)", p->channels);
+    if (p->filter < -1 || p->filter > 4) return fail(ctx, SM_E_ARG, "png: filter %d (-1 adaptive, 0..4)", p->filter);
+    if (disp && p->disp_mode != SM_PNG_DISP_KITTI && p->disp_mode != SM_PNG_DISP_LINEAR_U8)
+        return fail(ctx, SM_E_ARG, "png: disp_mode %d unknown", p->disp_mode);
+    const bool linear = disp && p->disp_mode == SM_PNG_DISP_LINEAR_U8;
+    if (linear && p->src_kind == SM_PNG_SRC_DISP_F32)
+        return fail(ctx, SM_E_UNSUPPORTED, "png: SM_PNG_DISP_LINEAR_U8 takes an int16 map");
+    if (linear && p->has_bounds && p->hi < p->lo) return fail(ctx, SM_E_ARG, "png: hi %d < lo %d", p->hi, p->lo);
+    const size_t esz = p->src_kind == SM_PNG_SRC_U8 ? 1 : p->src_kind == SM_PNG_SRC_DISP_F32 ? 4 : 2;
+    const size_t src_row = (size_t)W * esz * (size_t)p->channels;
+    if (row_stride < src_row) return fail(ctx, SM_E_ARG, "png: row_stride_bytes %zu smaller than a row (%zu)", row_stride, src_row);
+    if (nimg > 1 && img_stride < (size_t)(H - 1) * row_stride + src_row)
+        return fail(ctx, SM_E_ARG, "png: img_stride_bytes %zu smaller than one image", img_stride);
+    if (row_stride % esz || (nimg > 1 && img_stride % esz) || reinterpret_cast<uintptr_t>(img) % esz)
+        return fail(ctx, SM_E_ARG, "png: the image is not aligned to its %zu-byte samples", esz);
+    a = smk::PngArgs{};
+    a.img = static_cast<const uint8_t*>(img), a.img_stride = img_stride, a.row_stride = row_stride;
+    a.H = H, a.W = W;
+    a.kind = p->src_kind, a.channels = p->channels, a.keep = p->keep_channel_order != 0, a.filter = p->filter;
+    a.mode = disp ? p->disp_mode : 0;
+    a.lo = p->lo, a.hi = p->hi;
+    a.depth = (p->src_kind == SM_PNG_SRC_U16 || (disp && !linear)) ? 16 : 8;
+    a.out_channels = p->channels;
+    a.bpp = a.out_channels * a.depth / 8;
+    const uint64_t rowbytes = (uint64_t)W * a.bpp, stream = (rowbytes + 1) * (uint64_t)H;
+    if (stream >= (1ull << 31)) return fail(ctx, SM_E_UNSUPPORTED, "png: a filtered stream of %llu bytes (2^31 and more)", (unsigned long long)stream);
+    a.rowbytes = (uint32_t)rowbytes, a.stream_len = stream, a.stream_stride = (stream + 15) & ~15ull;
+    a.nseg = (uint32_t)((stream + smk::PNG_SEG - 1) / smk::PNG_SEG);
+    return SM_OK;
+}
+
+size_t png_bound_of(uint64_t stream, uint32_t nseg) { return (size_t)(57 + 6 + 17ull * nseg + stream); }
+
+}  // namespace
+
+size_t sm_png_bound(int H, int W, int channels, int depth)
+{
+    if (H <= 0 || W <= 0 || (channels != 1 && channels != 3) || (depth != 8 && depth != 16) || (channels == 3 && depth == 16))
+        return 0;
+    const uint64_t stream = ((uint64_t)W * channels * (depth / 8) + 1) * (uint64_t)H;
+    if (stream >= (1ull << 31)) return 0;
+    return png_bound_of(stream, (uint32_t)((stream + smk::PNG_SEG - 1) / smk::PNG_SEG));
+}
+
+int sm_png_encode_batch_device(sm_ctx* ctx, const void* d_img, size_t img_stride_bytes, size_t row_stride_bytes,
+                               int nimg, int H, int W, const sm_png_params* p, size_t capacity_bytes, uint8_t* d_out,
+                               uint64_t* d_nbytes)
+{
+    if (!ctx) return fail(nullptr, SM_E_ARG, "ctx is NULL");
+    smk::PngArgs a;
+    int rc;
+    if ((rc = png_setup(ctx, d_img, img_stride_bytes, row_stride_bytes, nimg, H, W, p, a)) != SM_OK) return rc;
+    if (!d_out && (capacity_bytes || !d_nbytes))
+        return fail(ctx, SM_E_ARG, "png: d_out NULL needs capacity 0 and d_nbytes (the size query)");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t nchunk = (size_t)nimg * a.nseg;
+    if ((rc = ensure(ctx, ctx->png_stream, (size_t)nimg * a.stream_stride)) != SM_OK) return rc;
+    if ((rc = ensure(ctx, ctx->png_slots, nchunk * smk::PNG_SLOT)) != SM_OK) return rc;
+    if ((rc = ensure(ctx, ctx->png_seg, nchunk * sizeof(smk::PngSegInfo))) != SM_OK) return rc;
+    if ((rc = ensure(ctx, ctx->png_off, nchunk * 8)) != SM_OK) return rc;
+    if ((rc = ensure(ctx, ctx->png_img, (size_t)nimg * sizeof(smk::PngImgInfo))) != SM_OK) return rc;
+    if (!d_nbytes) {
+        if ((rc = ensure(ctx, ctx->png_nb, (size_t)nimg * 8)) != SM_OK) return rc;
+        d_nbytes = (uint64_t*)ctx->png_nb.p;
+    }
+    a.stream = (uint8_t*)ctx->png_stream.p, a.slots = (uint8_t*)ctx->png_slots.p;
+    a.seginfo = (smk::PngSegInfo*)ctx->png_seg.p, a.offs = (uint64_t*)ctx->png_off.p;
+    a.imginfo = (smk::PngImgInfo*)ctx->png_img.p;
+    a.out = d_out, a.capacity = capacity_bytes, a.nbytes = d_nbytes;
+    const dim3 blk(smk::PNG_BLOCK);
+    if (a.kind == SM_PNG_SRC_DISP_I16 && a.mode == SM_PNG_DISP_LINEAR_U8 && !p->has_bounds) {
+        if ((rc = ensure(ctx, ctx->png_range, (size_t)nimg * 8)) != SM_OK) return rc;
+        int* keys = (int*)ctx->png_range.p;
+        HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)keys, 0x7FFFFFFF, 2 * (size_t)nimg, ctx->stream));
+        hipLaunchKernelGGL(smk::k_png_minmax, dim3(std::min(H, 64), nimg), blk, 0, ctx->stream, a, keys);
+        a.range = keys;
+    }
+    const dim3 fgrid((H + smk::PNG_FILTER_ROWS - 1) / smk::PNG_FILTER_ROWS, nimg);
+    if (a.rowbytes <= smk::PNG_MAX_ROW) {
+        const size_t flds = (size_t)(smk::PNG_FILTER_ROWS + 1) * ((a.rowbytes + 3u) & ~3u);
+        if (flds > 48 * 1024)  // above the default limit of dynamic LDS
+            HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(smk::k_png_filter<true>),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)flds));
+        hipLaunchKernelGGL(smk::k_png_filter<true>, fgrid, blk, flds, ctx->stream, a);
+    } else {
+        hipLaunchKernelGGL(smk::k_png_filter<false>, fgrid, blk, 0, ctx->stream, a);
+    }
+    const size_t dlds = sizeof(smk::PngDeflateLds);
+    HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(smk::k_png_deflate),
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)dlds));
+    hipLaunchKernelGGL(smk::k_png_deflate, dim3(a.nseg, nimg), dim3(smk::PNG_DBLOCK), dlds, ctx->stream, a);
+    hipLaunchKernelGGL(smk::k_png_assemble, dim3(nimg), blk, 0, ctx->stream, a);
+    if (d_out) hipLaunchKernelGGL(smk::k_png_scatter, dim3(a.nseg, nimg), blk, 0, ctx->stream, a);
+    HIP_TRY(ctx, hipGetLastError());
+    return SM_OK;
+}
+
+int sm_png_encode(sm_ctx* ctx, const void* img, size_t row_stride_bytes, int H, int W, const sm_png_params* p,
+                  size_t capacity_bytes, uint8_t* out, uint64_t* nbytes)
+{
+    if (!ctx) return fail(nullptr, SM_E_ARG, "ctx is NULL");
+    smk::PngArgs a;
+    int rc;
+    if ((rc = png_setup(ctx, img, 0, row_stride_bytes, 1, H, W, p, a)) != SM_OK) return rc;
+    if (!nbytes || (capacity_bytes && !out)) return fail(ctx, SM_E_ARG, "png: an output pointer is NULL");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t esz = a.kind == SM_PNG_SRC_U8 ? 1 : a.kind == SM_PNG_SRC_DISP_F32 ? 4 : 2;
+    const size_t ib = (size_t)(H - 1) * row_stride_bytes + (size_t)W * esz * a.channels;
+    const size_t bound = png_bound_of(a.stream_len, a.nseg);
+    if ((rc = ensure(ctx, ctx->png_in, ib)) != SM_OK) return rc;
+    if ((rc = ensure(ctx, ctx->png_out, bound)) != SM_OK) return rc;
+    if ((rc = ensure(ctx, ctx->png_nb, 8)) != SM_OK) return rc;
+    {
+        StageTimer t_(ctx, ctx->stream, SM_STAGE_H2D, 1);
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->png_in.p, img, ib, hipMemcpyHostToDevice, ctx->stream));
+    }
+    if ((rc = sm_png_encode_batch_device(ctx, ctx->png_in.p, 0, row_stride_bytes, 1, H, W, p, bound,
+                                         (uint8_t*)ctx->png_out.p, (uint64_t*)ctx->png_nb.p)) != SM_OK)
+        return rc;
+    uint64_t n = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(&n, ctx->png_nb.p, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    *nbytes = n;
+    if (n > capacity_bytes)
+        return fail(ctx, SM_E_ARG, "png: the file is %llu bytes, the capacity is %zu", (unsigned long long)n, capacity_bytes);
+    {
+        StageTimer t_(ctx, ctx->stream, SM_STAGE_D2H, 1);
+        HIP_TRY(ctx, hipMemcpyAsync(out, ctx->png_out.p, n, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return SM_OK;
+}
+
+int sm_png_encode_host(const void* img, size_t row_stride_bytes, int H, int W, const sm_png_params* p,
+                       size_t capacity_bytes, uint8_t* out, uint64_t* nbytes)
+{
+    smk::PngArgs a;
+    int rc;
+    if ((rc = png_setup(nullptr, img, 0, row_stride_bytes, 1, H, W, p, a)) != SM_OK) return rc;
+    if (!nbytes || (capacity_bytes && !out)) return fail(nullptr, SM_E_ARG, "png: an output pointer is NULL");
+    if (a.kind == SM_PNG_SRC_DISP_I16 && a.mode == SM_PNG_DISP_LINEAR_U8 && !p->has_bounds) {
+        int lo = 0x7FFFFFFF, hi = -0x7FFFFFFF;
+        for (int y = 0; y < H; ++y) {
+            const int16_t* row = reinterpret_cast<const int16_t*>(a.img + (size_t)y * row_stride_bytes);
+            for (int x = 0; x < W; ++x) lo = std::min(lo, (int)row[x]), hi = std::max(hi, (int)row[x]);
+        }
+        a.lo = lo, a.hi = hi;
+    }
+    std::vector<uint8_t> file;
+    smk::png_encode_host(a, file);
+    *nbytes = file.size();
+    if (file.size() > capacity_bytes)
+        return fail(nullptr, SM_E_ARG, "png: the file is %zu bytes, the capacity is %zu", file.size(), capacity_bytes);
+    std::memcpy(out, file.data(), file.size());
     return SM_OK;
 }
 

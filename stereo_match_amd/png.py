@@ -1,0 +1,203 @@
+"""PNG output on the GPU: what the reference's scripts hand to ``cv2.imwrite``
+(``disparity_calculation.py:247-248,278-279,290-291``, ``rectified_img_cal.py:316-319``,
+``disparity_test.py:114-115``, ``try_try.py:155,190``) and the KITTI disparity format, encoded
+where the images already are:
+
+* :func:`imencode_png`, :func:`imwrite` — uint8 gray, uint8 BGR and uint16 gray images, numpy
+  arrays or torch CUDA tensors (``sm_png_encode*``); :func:`imencode_png_batch` for a CUDA batch;
+* :func:`encode_disparity_png`, :func:`write_disparity_png` — an int16 x16 or float32 disparity
+  map as the KITTI 16-bit PNG (disparity * 256, 0 invalid) or as a min-max uint8 picture
+  (``show_disparity``'s ``normalize(NORM_MINMAX)``, ``plot_functions.py:99-100``), converted
+  inside the filter kernel;
+* :func:`imencode_png_host` — the same file from the same functions on the CPU.
+
+The files are standard PNGs (one IDAT chunk per 32 KiB of the filtered stream); the filter choice
+and the coder are the package's own and documented in ``include/stereo_match_amd.h``.  The integer
+rounding of the min-max picture is this package's contract: OpenCV's ``normalize`` is not pinned.
+"""
+from __future__ import annotations
+
+import os
+
+import numpy as np
+
+from . import _lib
+
+
+def _is_torch(x) -> bool:
+    return type(x).__module__.startswith("torch")
+
+
+def _unsupported(msg):
+    raise _lib.SmError(_lib.SM_E_UNSUPPORTED, msg)
+
+
+def _image_params(dtype_name: str, shape, filter, keep_channel_order) -> _lib.SmPngParams:
+    p = _lib.SmPngParams()
+    nd = len(shape)
+    if dtype_name == "uint8" and (nd == 2 or (nd == 3 and shape[2] in (1, 3))):
+        p.src_kind, p.channels = _lib.SM_PNG_SRC_U8, (3 if nd == 3 and shape[2] == 3 else 1)
+    elif dtype_name == "uint16" and (nd == 2 or (nd == 3 and shape[2] == 1)):
+        p.src_kind, p.channels = _lib.SM_PNG_SRC_U16, 1
+    else:
+        _unsupported(f"PNG output takes uint8 [H, W], uint8 [H, W, 3] and uint16 [H, W] images, not {dtype_name} "
+                     f"{tuple(shape)}")
+    p.keep_channel_order = int(bool(keep_channel_order))
+    p.filter = -1 if filter is None else int(filter)
+    return p
+
+
+def _disp_params(dtype_name: str, shape, fmt, lo, hi, filter) -> _lib.SmPngParams:
+    p = _lib.SmPngParams()
+    if len(shape) != 2 or dtype_name not in ("int16", "float32"):
+        raise ValueError(f"disparity must be a 2-D int16 (x16) or float32 map, not {dtype_name} {tuple(shape)}")
+    p.src_kind = _lib.SM_PNG_SRC_DISP_I16 if dtype_name == "int16" else _lib.SM_PNG_SRC_DISP_F32
+    p.channels = 1
+    p.filter = -1 if filter is None else int(filter)
+    if fmt == "kitti":
+        p.disp_mode = _lib.SM_PNG_DISP_KITTI
+        if lo is not None or hi is not None:
+            raise ValueError("fmt='kitti' takes no bounds")
+    elif fmt == "u8":
+        p.disp_mode = _lib.SM_PNG_DISP_LINEAR_U8
+        if (lo is None) != (hi is None):
+            raise ValueError("give both lo and hi (in the map's own units), or neither for the map's min and max")
+        if lo is not None:
+            p.has_bounds, p.lo, p.hi = 1, int(lo), int(hi)
+    else:
+        raise ValueError(f"fmt must be 'kitti' or 'u8', not {fmt!r}")
+    return p
+
+
+def _torch_rows(t):
+    """A tensor whose pixels are contiguous: (tensor, row stride in bytes)."""
+    inner = 1
+    ok = True
+    for d in range(t.dim() - 1, 0, -1):
+        ok = ok and t.stride(d) == inner
+        inner *= t.shape[d]
+    if not ok or t.stride(0) < inner:
+        t = t.contiguous()
+    return t, t.stride(0) * t.element_size()
+
+
+def _encode_device(t, prm, nimg, H, W, img_stride, row_stride):
+    """nimg files of a CUDA tensor on torch's current stream: a list of bytes, through pinned
+    host memory."""
+    import torch
+
+    eng = _lib.engine(t.device.index or 0)
+    eng.set_stream(torch.cuda.current_stream(t.device).cuda_stream)
+    cap = _lib.load().sm_png_bound(H, W, *_lib.png_file_geometry(prm))
+    if cap == 0:
+        _unsupported(f"PNG output: an image of {W}x{H} is too large")
+    cap = (cap + 15) & ~15
+    out = torch.empty((nimg, cap), dtype=torch.uint8, device=t.device)
+    nb = torch.empty(nimg, dtype=torch.int64, device=t.device)
+    eng.png_encode_batch_device(t.data_ptr(), img_stride, row_stride, nimg, H, W, prm, cap, out.data_ptr(), nb.data_ptr())
+    nb_h = torch.empty(nimg, dtype=torch.int64, pin_memory=True)
+    nb_h.copy_(nb, non_blocking=True)
+    torch.cuda.current_stream(t.device).synchronize()
+    sizes = [int(x) for x in nb_h]
+    host = torch.empty((nimg, max(sizes)), dtype=torch.uint8, pin_memory=True)
+    host.copy_(out[:, :max(sizes)], non_blocking=True)
+    torch.cuda.current_stream(t.device).synchronize()
+    h = host.numpy()
+    return [h[i, :sizes[i]].tobytes() for i in range(nimg)]
+
+
+def _numpy_image(img):
+    a = np.asarray(img)
+    if a.ndim == 3 and a.shape[2] == 1:
+        a = a[:, :, 0]
+    if a.size == 0:
+        raise ValueError("empty image")
+    inner = a.itemsize
+    ok = True
+    for d in range(a.ndim - 1, 0, -1):
+        ok = ok and a.strides[d] == inner
+        inner *= a.shape[d]
+    if not ok or a.strides[0] < inner:
+        a = np.ascontiguousarray(a)
+    return a
+
+
+def _encode(img, make_params, device, host):
+    if _is_torch(img):
+        if host:
+            img = img.cpu().numpy()
+        else:
+            if not img.is_cuda:
+                raise ValueError("a torch image must be a CUDA tensor (or pass a numpy array)")
+            if img.numel() == 0:
+                raise ValueError("empty image")
+            if img.dim() == 3 and img.shape[2] == 1:
+                img = img[:, :, 0]
+            prm = make_params(str(img.dtype).replace("torch.", ""), tuple(img.shape))
+            t, row_stride = _torch_rows(img)
+            return _encode_device(t, prm, 1, t.shape[0], t.shape[1], 0, row_stride)[0]
+    a = _numpy_image(img)
+    prm = make_params(a.dtype.name, a.shape)
+    if host:
+        return _lib.png_encode_host(a, prm).tobytes()
+    return _lib.engine(device).png_encode(a, prm).tobytes()
+
+
+def imencode_png(img, *, filter=None, keep_channel_order=False, device=0) -> bytes:
+    """The PNG file of ``img`` as ``bytes``: uint8 ``[H, W]`` (gray), uint8 ``[H, W, 3]`` (BGR in
+    memory, RGB in the file, as ``cv2.imwrite``; ``keep_channel_order`` for an RGB source) or
+    uint16 ``[H, W]``; a numpy array (uploaded, synchronous) or a torch CUDA tensor (encoded in
+    place on torch's current stream, the bytes through pinned host memory).  ``filter``: ``None``
+    picks a scanline filter per row, 0..4 fixes it.  Other dtypes or shapes raise
+    ``SmError(SM_E_UNSUPPORTED)``."""
+    return _encode(img, lambda dt, sh: _image_params(dt, sh, filter, keep_channel_order), device, False)
+
+
+def imencode_png_host(img, *, filter=None, keep_channel_order=False) -> bytes:
+    """:func:`imencode_png` on the CPU (``sm_png_encode_host``): the same bytes, no device."""
+    return _encode(img, lambda dt, sh: _image_params(dt, sh, filter, keep_channel_order), 0, True)
+
+
+def imencode_png_batch(imgs, *, filter=None, keep_channel_order=False):
+    """The files of a uint8 CUDA batch ``[N, H, W]`` or ``[N, H, W, 3]`` (or uint16 ``[N, H, W]``)
+    from one call: a list of ``bytes``, each equal to the image's own :func:`imencode_png`."""
+    if not _is_torch(imgs) or not imgs.is_cuda or imgs.dim() not in (3, 4):
+        raise ValueError("imencode_png_batch takes a CUDA tensor [N, H, W] or [N, H, W, 3]")
+    if imgs.numel() == 0:
+        raise ValueError("empty batch")
+    prm = _image_params(str(imgs.dtype).replace("torch.", ""), tuple(imgs.shape[1:]), filter, keep_channel_order)
+    t = imgs.contiguous()
+    n, H, W = t.shape[:3]
+    row = t.stride(1) * t.element_size()
+    return _encode_device(t, prm, n, H, W, t.stride(0) * t.element_size(), row)
+
+
+def imwrite(filename, img, *, device=0) -> bool:
+    """``cv2.imwrite(filename, img)`` for ``.png`` files (BGR in memory, RGB in the file).  Another
+    extension raises ``SmError(SM_E_UNSUPPORTED)``."""
+    if os.path.splitext(str(filename))[1].lower() != ".png":
+        _unsupported(f"imwrite writes .png files, not {filename!r}")
+    data = imencode_png(img, device=device)
+    with open(filename, "wb") as f:
+        f.write(data)
+    return True
+
+
+def encode_disparity_png(disp, fmt="kitti", lo=None, hi=None, *, filter=None, device=0, host=False) -> bytes:
+    """A disparity map (int16 x16, or float32 in pixels; numpy or torch CUDA) as a PNG file.
+
+    ``fmt="kitti"``: 16-bit gray, value = disparity * 256, 0 = invalid (int16 ``d < 0 -> 0``, else
+    ``min(65535, d << 4)``; float32 non-finite or ``<= 0 -> 0``, else ``min(65535, rint(d * 256))``).
+    ``fmt="u8"`` (int16 maps): 8-bit gray ``clamp((d - lo) * 255 / (hi - lo), 0, 255)`` rounded half
+    up in integers, ``lo`` / ``hi`` in the map's own units, or the map's minimum and maximum when
+    left out (found on the device); ``hi == lo`` gives 0 everywhere.  ``host=True`` encodes on the
+    CPU."""
+    return _encode(disp, lambda dt, sh: _disp_params(dt, sh, fmt, lo, hi, filter), device, host)
+
+
+def write_disparity_png(filename, disp, fmt="kitti", lo=None, hi=None, *, device=0) -> bool:
+    """:func:`encode_disparity_png` into a file."""
+    data = encode_disparity_png(disp, fmt, lo, hi, device=device)
+    with open(filename, "wb") as f:
+        f.write(data)
+    return True
