@@ -37,6 +37,7 @@ extern "C" {
 #define SM_E_ARG (-1)         /* bad argument: mirrors OpenCV's CV_Assert failures */
 #define SM_E_HIP (-2)         /* HIP runtime / launch error */
 #define SM_E_UNSUPPORTED (-4) /* valid for OpenCV but not implemented / outside exact range */
+#define SM_E_DATA (-5)        /* corrupt input data (a PNG file that does not decode) */
 
 #define SM_COST_SGBM 0   /* OpenCV StereoSGBM cost: BT(Sobel-x clip) + BT(raw)>>2, blockSize^2 box */
 #define SM_COST_CENSUS 1 /* north-star cost: 9x7 census + Hamming (no reference counterpart) */
@@ -434,6 +435,74 @@ int sm_png_encode(sm_ctx* ctx, const void* img, size_t row_stride_bytes, int H, 
  * stream). */
 int sm_png_encode_host(const void* img, size_t row_stride_bytes, int H, int W, const sm_png_params* p,
                        size_t capacity_bytes, uint8_t* out, uint64_t* nbytes);
+
+/* ---- PNG input: cv2.imread(".png") of the reference's scripts
+ * (disparity_test.py:79-80, mapTo3D.py:78-79, mapTo3D_mc_cnn.py:70-77) and KITTI 16-bit disparity
+ * maps, decoded on the device: chunk walk, CRC-32 of every chunk up to IEND, inflate, Adler-32,
+ * scanline unfilter, pixel conversion.
+ *
+ * Files: non-interlaced; colour type 0 at depth 8 or 16, colour type 2 at depth 8, colour type 6
+ * at depth 8 (alpha dropped); (W*bpp + 1)*H < 2^31 as for output.  Ancillary chunks are skipped.
+ * Interlace, palette, depths 1/2/4, 16-bit colour and gray+alpha are SM_E_UNSUPPORTED with a
+ * message that names the field.
+ * Inflate: the IDAT chunks are first inflated each on its own (a wave per chunk), which is exact
+ * when every chunk is a run of whole deflate blocks ending on a byte boundary that never reaches
+ * back before itself and makes at most SM_PNGDEC_CAP bytes (the files of sm_png_encode*, or
+ * pieces closed by Z_FULL_FLUSH); an image that fails any of these checks, or has more than
+ * 2*ceil(stream/SM_PNGDEC_CAP) + 4 IDAT chunks, is inflated serially (a wave per image), which is
+ * exact for every zlib stream.
+ * Output by out_kind and flags (cv2.imread's): SM_PNGDEC_U8 with flags 1 -> BGR uint8 [H][W][3]
+ * (gray replicated, 16-bit samples >> 8; RGB order with keep_channel_order), flags 0 -> gray
+ * uint8 [H][W] (a colour file through (1868*B + 9617*G + 4899*R + 8192) >> 14, sm_bgr2gray_u8's
+ * formula; OpenCV's decoder-side conversion is not pinned), flags -1 -> the file's own channels
+ * (8-bit files); SM_PNGDEC_U16 (flags -1, 16-bit gray files) -> uint16 [H][W];
+ * SM_PNGDEC_DISP_I16 / _F32 (16-bit gray files, SM_PNG_DISP_KITTI): v != 0 ? v >> 4 : invalid_i16
+ * (int16 x16) and v != 0 ? v / 256.f : invalid_f32. */
+#define SM_PNGDEC_CAP 32768
+#define SM_PNGDEC_U8 0
+#define SM_PNGDEC_U16 1
+#define SM_PNGDEC_DISP_I16 2
+#define SM_PNGDEC_DISP_F32 3
+typedef struct sm_pngdec_params {
+    int out_kind;           /* SM_PNGDEC_* */
+    int flags;              /* 1, 0, -1 as cv2.imread (SM_PNGDEC_U8; -1 for the other kinds) */
+    int keep_channel_order; /* 3-channel output: 0 gives BGR, 1 the file's RGB */
+    int disp_mode;          /* SM_PNG_DISP_KITTI (disparity kinds) */
+    int invalid_i16;        /* SM_PNGDEC_DISP_I16: the value of a 0 sample */
+    float invalid_f32;      /* SM_PNGDEC_DISP_F32: the value of a 0 sample */
+    int file_channels;      /* of the files: 1, 3, or 4 (RGBA); 0: taken from the file (host-pointer calls) */
+    int file_depth;         /* 8 or 16; 0 as above */
+    int max_chunks;         /* batch: chunks a file may have; 0: 2*ceil(stream/SM_PNG_SEG) + 64 */
+    uint64_t max_file_bytes;/* batch: bytes a file may have; 0: twice sm_png_bound of the geometry */
+} sm_pngdec_params;
+
+/* IHDR of a PNG file in host memory: *channels 1, 3 or 4 (RGBA), *depth 8 or 16.  SM_E_DATA for
+ * bytes that are no PNG file, SM_E_UNSUPPORTED for a file this package does not decode.  Host
+ * only, no context. */
+int sm_png_info(const uint8_t* file, size_t nbytes, int* H, int* W, int* channels, int* depth);
+/* nimg files of one geometry (H, W, p->file_channels, p->file_depth) in device memory, file i at
+ * d_files + d_offsets[i] with d_sizes[i] bytes: image i to d_out + i*img_stride_bytes, rows
+ * row_stride_bytes apart.  d_status[i]: 0, or a positive code of the first fault found in file i
+ * (sm_pngdec_status_message); the pixels of such an image are undefined.  Asynchronous. */
+int sm_png_decode_batch_device(sm_ctx* ctx, const uint8_t* d_files, const uint64_t* d_offsets, const uint64_t* d_sizes,
+                               int nimg, int H, int W, const sm_pngdec_params* p, void* d_out, size_t img_stride_bytes,
+                               size_t row_stride_bytes, int* d_status);
+/* One file on host pointers (H x W pixels of the output kind at `out`).  A faulty file is
+ * SM_E_DATA (not a PNG, truncated, corrupt) or SM_E_UNSUPPORTED with the message of its status;
+ * *status (may be NULL) gets the code.  Synchronous. */
+int sm_png_decode(sm_ctx* ctx, const uint8_t* file, size_t nbytes, const sm_pngdec_params* p, void* out,
+                  size_t row_stride_bytes, int* status);
+/* The same pixels, status and inflate path by the same functions on the CPU.  Needs no context
+ * and no device. */
+int sm_png_decode_host(const uint8_t* file, size_t nbytes, const sm_pngdec_params* p, void* out,
+                       size_t row_stride_bytes, int* status);
+/* How many images of the last decode call took the chunk-parallel and the serial inflate path
+ * (ctx NULL: the last sm_png_decode_host of this thread).  Synchronises the stream. */
+int sm_png_decode_stats(sm_ctx* ctx, int* n_parallel, int* n_serial);
+/* The message of a status code of the decoder, and the SM_E_* code the host-pointer calls return
+ * for it (SM_OK, SM_E_DATA or SM_E_UNSUPPORTED). */
+const char* sm_pngdec_status_message(int status);
+int sm_pngdec_status_code(int status);
 
 /* ---- StereoBM (the reference's method="BM" branch,
  * stereo_vision/stereo_vision.py:164-166: cv2.StereoBM_create(numDisparities,

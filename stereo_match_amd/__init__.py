@@ -19,6 +19,9 @@ Public surface (mirrors the reference / OpenCV names the reference uses):
 * :func:`imwrite`, :func:`imencode_png`, :func:`imencode_png_batch`, :func:`imencode_png_host`,
   :func:`write_disparity_png`, :func:`encode_disparity_png` — PNG files (``cv2.imwrite``,
   ``disparity_calculation.py:247-291``) and the KITTI 16-bit disparity format, encoded on the device
+* :func:`imread`, :func:`imdecode`, :func:`imdecode_batch`, :func:`imdecode_host`,
+  :func:`read_disparity_png`, :func:`decode_disparity_png` — PNG files read back (``cv2.imread``,
+  ``disparity_test.py:79-80``, ``mapTo3D.py:78-79``), decoded on the device
 
 All compute runs in ``libstereo_match_amd.so`` (HIP, gfx950) through the
 C-ABI in ``include/stereo_match_amd.h``; there is no CPU fallback.
@@ -34,8 +37,8 @@ from .rectify import (CALIB_ZERO_DISPARITY, COLOR_BGR2GRAY, CV_32FC1, INTER_LINE
                       initUndistortRectifyMap, rectify_opencv, remap, stereoRectify)
 from .denoise import fastNlMeansDenoising
 from .pointcloud import extract_point_cloud, format_ply, write_point_cloud
-from .png import (encode_disparity_png, imencode_png, imencode_png_batch, imencode_png_host, imwrite,
-                  write_disparity_png)
+from .png import (decode_disparity_png, encode_disparity_png, imdecode, imdecode_batch, imdecode_host, imencode_png,
+                  imencode_png_batch, imencode_png_host, imread, imwrite, read_disparity_png, write_disparity_png)
 from . import filters
 from .filters import gaussian_filter, image_measure, pyrDown
 
@@ -48,7 +51,8 @@ __all__ = [
     "CALIB_ZERO_DISPARITY", "CV_32FC1", "INTER_LINEAR", "COLOR_BGR2GRAY", "fastNlMeansDenoising",
     "extract_point_cloud", "format_ply", "write_point_cloud",
     "imwrite", "imencode_png", "imencode_png_batch", "imencode_png_host", "write_disparity_png",
-    "encode_disparity_png",
+    "encode_disparity_png", "imread", "imdecode", "imdecode_batch", "imdecode_host", "read_disparity_png",
+    "decode_disparity_png",
     "filters", "gaussian_filter", "image_measure", "pyrDown",
 ]
 __version__ = "0.1.0"

@@ -19,6 +19,7 @@ LIB_PATH = os.environ.get("STEREO_MATCH_AMD_LIB") or os.path.join(_HERE, "libste
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "stereo_match_amd.h")
 
 SM_OK, SM_E_ARG, SM_E_HIP, SM_E_UNSUPPORTED = 0, -1, -2, -4
+SM_E_DATA = -5
 SM_COST_SGBM, SM_COST_CENSUS, SM_COST_VOLUME = 0, 1, 2
 SM_MODE_SGBM, SM_MODE_HH = 5, 8
 TIMING_ONLY = 0x40000000  # include/stereo_match_amd.h SM_TIMING_ONLY
@@ -80,7 +81,18 @@ class SmPngParams(ctypes.Structure):
         "src_kind", "channels", "keep_channel_order", "filter", "disp_mode", "has_bounds", "lo", "hi")]
 
 
+class SmPngDecParams(ctypes.Structure):
+    """Mirror of ``struct sm_pngdec_params`` (PNG input: output kind, imread flags, disparity
+    conversion, the files' geometry and limits)."""
+    _fields_ = [("out_kind", ctypes.c_int), ("flags", ctypes.c_int), ("keep_channel_order", ctypes.c_int),
+                ("disp_mode", ctypes.c_int), ("invalid_i16", ctypes.c_int), ("invalid_f32", ctypes.c_float),
+                ("file_channels", ctypes.c_int), ("file_depth", ctypes.c_int), ("max_chunks", ctypes.c_int),
+                ("max_file_bytes", ctypes.c_uint64)]
+
+
 SM_PNG_SEG = 32768
+SM_PNGDEC_CAP = 32768
+SM_PNGDEC_U8, SM_PNGDEC_U16, SM_PNGDEC_DISP_I16, SM_PNGDEC_DISP_F32 = 0, 1, 2, 3
 SM_PNG_SRC_U8, SM_PNG_SRC_U16, SM_PNG_SRC_DISP_I16, SM_PNG_SRC_DISP_F32 = 0, 1, 2, 3
 SM_PNG_DISP_KITTI, SM_PNG_DISP_LINEAR_U8 = 0, 1
 PLY_MAX_ROW = 157  # bytes of the longest row '%f %f %f %d %d %d ' + newline
@@ -188,6 +200,18 @@ _SIGS = {
                                  _c.c_size_t, _c.c_void_p, _c.POINTER(_c.c_uint64)]),
     "sm_png_encode_host": (_c.c_int, [_c.c_void_p, _c.c_size_t, _c.c_int, _c.c_int, _c.POINTER(SmPngParams),
                                       _c.c_size_t, _c.c_void_p, _c.POINTER(_c.c_uint64)]),
+    "sm_png_info": (_c.c_int, [_c.c_void_p, _c.c_size_t, _c.POINTER(_c.c_int), _c.POINTER(_c.c_int),
+                               _c.POINTER(_c.c_int), _c.POINTER(_c.c_int)]),
+    "sm_png_decode_batch_device": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int,
+                                              _c.c_int, _c.POINTER(SmPngDecParams), _c.c_void_p, _c.c_size_t,
+                                              _c.c_size_t, _c.c_void_p]),
+    "sm_png_decode": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.POINTER(SmPngDecParams), _c.c_void_p,
+                                 _c.c_size_t, _c.POINTER(_c.c_int)]),
+    "sm_png_decode_host": (_c.c_int, [_c.c_void_p, _c.c_size_t, _c.POINTER(SmPngDecParams), _c.c_void_p, _c.c_size_t,
+                                      _c.POINTER(_c.c_int)]),
+    "sm_png_decode_stats": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_int), _c.POINTER(_c.c_int)]),
+    "sm_pngdec_status_message": (_c.c_char_p, [_c.c_int]),
+    "sm_pngdec_status_code": (_c.c_int, [_c.c_int]),
     "sm_bm_default_params": (_c.c_int, [_c.c_int, _c.c_int, _c.POINTER(SmBmParams)]),
     "sm_bm_right_matcher_params": (_c.c_int, [_c.POINTER(SmBmParams), _c.POINTER(SmBmParams)]),
     "sm_bm_compute": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int,
@@ -276,6 +300,36 @@ def png_encode_host(img: np.ndarray, prm: "SmPngParams", capacity: int = None) -
     if rc != SM_OK:
         _raise(rc, None)
     return out[:nb.value]
+
+
+def png_info(buf):
+    """sm_png_info: (H, W, channels, depth) of a PNG file held in a bytes-like object.  Host only."""
+    b = np.frombuffer(buf, np.uint8)
+    v = [ctypes.c_int() for _ in range(4)]
+    rc = load().sm_png_info(b.ctypes.data if b.size else np.zeros(1, np.uint8).ctypes.data, b.size, *[ctypes.byref(x) for x in v])
+    if rc != SM_OK:
+        _raise(rc, None)
+    return tuple(x.value for x in v)
+
+
+def png_decode_stats(ctx=None):
+    """sm_png_decode_stats: (parallel, serial) images of the last decode call of this context, or
+    (ctx None) of this thread's last sm_png_decode_host."""
+    a, b = ctypes.c_int(), ctypes.c_int()
+    rc = load().sm_png_decode_stats(ctx, ctypes.byref(a), ctypes.byref(b))
+    if rc != SM_OK:
+        _raise(rc, ctx)
+    return a.value, b.value
+
+
+def png_decode_host(buf, prm: "SmPngDecParams", out: np.ndarray):
+    """sm_png_decode_host into ``out`` (rows ``out.strides[0]`` apart), decoded on the CPU by the
+    functions the GPU kernels run.  Needs no context and no device."""
+    b = np.frombuffer(buf, np.uint8)
+    rc = load().sm_png_decode_host(b.ctypes.data, b.size, ctypes.byref(prm), out.ctypes.data, out.strides[0], None)
+    if rc != SM_OK:
+        _raise(rc, None)
+    return out
 
 
 def volume_scale(scale) -> float:
@@ -673,6 +727,22 @@ class Engine:
                                             ctypes.byref(prm), out.size, out.ctypes.data if out.size else None,
                                             ctypes.byref(nb)))
         return out[:nb.value]
+
+    def png_decode(self, buf, prm: "SmPngDecParams", out: np.ndarray) -> np.ndarray:
+        """sm_png_decode: one file in host memory into the host array ``out`` (decoded on the device)."""
+        b = np.frombuffer(buf, np.uint8)
+        self._check(self._lib.sm_png_decode(self.ctx, b.ctypes.data, b.size, ctypes.byref(prm), out.ctypes.data,
+                                            out.strides[0], None))
+        return out
+
+    def png_decode_batch_device(self, d_files: int, d_offsets: int, d_sizes: int, nimg: int, H: int, W: int,
+                                prm: "SmPngDecParams", d_out: int, img_stride: int, row_stride: int, d_status: int):
+        self._check(self._lib.sm_png_decode_batch_device(self.ctx, d_files, d_offsets, d_sizes, nimg, H, W,
+                                                         ctypes.byref(prm), d_out, img_stride, row_stride, d_status))
+
+    def png_decode_stats(self):
+        """(parallel, serial): the inflate paths of the images of the last decode call."""
+        return png_decode_stats(self.ctx)
 
     def png_encode_batch_device(self, d_img: int, img_stride: int, row_stride: int, nimg: int, H: int, W: int,
                                 prm: "SmPngParams", capacity_bytes: int, d_out: int, d_nbytes: int):

@@ -37,6 +37,7 @@
 #include "sm_filter.hpp"
 #include "sm_cloud.hpp"
 #include "sm_png.hpp"
+#include "sm_pngdec.hpp"
 #include "sm_bm.hpp"
 #include "sm_wide.hpp"
 #include "sm_sweep_host.hpp"
@@ -156,6 +157,12 @@ struct sm_ctx {
     // PNG output (sm_png.hpp): the filtered streams, the segments' data and records, the chunk
     // offsets, per-image records, min / max keys; image, files and sizes of the host entry point
     DevBuf png_stream, png_slots, png_seg, png_off, png_img, png_range, png_in, png_out, png_nb;
+    // PNG input (sm_pngdec.hpp): per-image records, chunk tables, the chunks' slots and records, the
+    // concatenated IDAT data, the filtered streams, Adler pieces, the carried rows; the staged
+    // file, its offset / size pair, the pixels and the status of the host-pointer call
+    DevBuf pd_img, pd_chunks, pd_idat, pd_cinfo, pd_slots, pd_zbuf, pd_stream, pd_seg, pd_carry, pd_in, pd_tab, pd_out,
+        pd_status;
+    int pd_last_nimg = 0;
     DevBuf flt_a;  // image_measure: the first Gaussian's result, [img][H][W] float64
     DevBuf wls_num, wls_den, wls_inter, wls_w, wls_disp[2], wls_out;  // WLS scratch
     DevBuf wls_R, wls_IT;         // WLS: Thomas pivots / elimination factors of every pass
@@ -2529,7 +2536,10 @@ void sm_destroy(sm_ctx* ctx)
                       &ctx->rm_gray, &ctx->nlm_tab, &ctx->cl_tot,    &ctx->cl_off,      &ctx->ply_tot,
                       &ctx->ply_off, &ctx->cl_verts, &ctx->cl_colors, &ctx->cl_out,      &ctx->flt_a,
                       &ctx->png_stream, &ctx->png_slots, &ctx->png_seg, &ctx->png_off, &ctx->png_img,
-                      &ctx->png_range, &ctx->png_in, &ctx->png_out, &ctx->png_nb};
+                      &ctx->png_range, &ctx->png_in, &ctx->png_out, &ctx->png_nb,
+                      &ctx->pd_img, &ctx->pd_chunks, &ctx->pd_idat, &ctx->pd_cinfo, &ctx->pd_slots, &ctx->pd_zbuf,
+                      &ctx->pd_stream, &ctx->pd_seg, &ctx->pd_carry, &ctx->pd_in, &ctx->pd_tab, &ctx->pd_out,
+                      &ctx->pd_status};
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (auto& bs : ctx->set) {
@@ -4057,6 +4067,252 @@ int sm_png_encode_host(const void* img, size_t row_stride_bytes, int H, int W, c
     if (file.size() > capacity_bytes)
         return fail(nullptr, SM_E_ARG, "png: the file is %zu bytes, the capacity is %zu", file.size(), capacity_bytes);
     std::memcpy(out, file.data(), file.size());
+    return SM_OK;
+}
+
+// ---- PNG input (sm_pngdec.hpp)
+namespace {
+
+thread_local int g_pd_host_path[2] = {0, 0};  // the last sm_png_decode_host: parallel, serial
+
+int pngdec_code(int status)
+{
+    if (status == smk::PD_OK) return SM_OK;
+    return (status >= smk::PD_E_INTERLACE && status <= smk::PD_E_SIZE) ? SM_E_UNSUPPORTED : SM_E_DATA;
+}
+
+int pngdec_fail(sm_ctx* ctx, int status, int index)
+{
+    const int code = pngdec_code(status);
+    if (index >= 0) return fail(ctx, code, "png decode: image %d: %s", index, smk::pngdec_message(status));
+    return fail(ctx, code, "png decode: %s", smk::pngdec_message(status));
+}
+
+// IHDR of a file in host memory: a status of the decoder
+int pngdec_info(const uint8_t* f, size_t n, smk::PdHdr& h)
+{
+    const uint8_t sig[8] = {0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A};
+    if (n < 8 || std::memcmp(f, sig, 8) != 0) return smk::PD_E_SIG;
+    if (n < 33) return smk::PD_E_TRUNC;
+    if (smk::pd_be32(f + 8) != 13u || std::memcmp(f + 12, "IHDR", 4) != 0) return smk::PD_E_IHDR;
+    return smk::pd_ihdr(f + 16, h);
+}
+
+// the checks and the geometry of all entry points (ctx NULL: the CPU twin)
+int pngdec_setup(sm_ctx* ctx, int nimg, int H, int W, const sm_pngdec_params* p, int fch, int fdepth, const void* out,
+                 size_t img_stride, size_t row_stride, smk::PdArgs& a)
+{
+    if (!p || !out) return fail(ctx, SM_E_ARG, "png decode: a required pointer is NULL");
+    if (nimg < 1 || nimg > 65535) return fail(ctx, SM_E_ARG, "png decode: nimg %d", nimg);
+    if (H < 1 || W < 1) return fail(ctx, SM_E_ARG, "png decode: empty image (%dx%d)", W, H);
+    if ((fch != 1 && fch != 3 && fch != 4) || (fdepth != 8 && fdepth != 16) || (fdepth == 16 && fch != 1))
+        return fail(ctx, SM_E_ARG, "png decode: file_channels %d at file_depth %d (1 at 8 or 16; 3 or 4 at 8)", fch, fdepth);
+    if (p->out_kind < SM_PNGDEC_U8 || p->out_kind > SM_PNGDEC_DISP_F32)
+        return fail(ctx, SM_E_ARG, "png decode: out_kind %d unknown", p->out_kind);
+    if (p->flags < -1 || p->flags > 1) return fail(ctx, SM_E_ARG, "png decode: flags %d (1, 0 or -1)", p->flags);
+    a = smk::PdArgs{};
+    a.kind = p->out_kind, a.keep = p->keep_channel_order != 0, a.inv_i16 = p->invalid_i16, a.inv_f32 = p->invalid_f32;
+    size_t opb;
+    if (p->out_kind == SM_PNGDEC_U8) {
+        if (p->flags == -1 && fdepth == 16)
+            return fail(ctx, SM_E_ARG, "png decode: flags -1 on a 16-bit file needs out_kind SM_PNGDEC_U16");
+        a.out_ch = p->flags == 1 ? 3 : p->flags == 0 ? 1 : (fch == 1 ? 1 : 3);
+        opb = (size_t)a.out_ch;
+    } else {
+        if (fdepth != 16 || fch != 1)
+            return fail(ctx, SM_E_UNSUPPORTED, "png decode: out_kind %d takes a 16-bit gray file, not %d channel(s) at depth %d",
+                        p->out_kind, fch, fdepth);
+        if (p->flags != -1) return fail(ctx, SM_E_ARG, "png decode: out_kind %d takes flags -1", p->out_kind);
+        if (p->out_kind != SM_PNGDEC_U16 && p->disp_mode != SM_PNG_DISP_KITTI)
+            return fail(ctx, SM_E_UNSUPPORTED, "png decode: only SM_PNG_DISP_KITTI maps are read back");
+        a.out_ch = 1;
+        opb = p->out_kind == SM_PNGDEC_DISP_F32 ? 4 : 2;
+    }
+    const size_t esz = p->out_kind == SM_PNGDEC_U8 ? 1 : opb;
+    if (row_stride < (size_t)W * opb)
+        return fail(ctx, SM_E_ARG, "png decode: row_stride_bytes %zu smaller than a row (%zu)", row_stride, (size_t)W * opb);
+    if (nimg > 1 && img_stride < (size_t)(H - 1) * row_stride + (size_t)W * opb)
+        return fail(ctx, SM_E_ARG, "png decode: img_stride_bytes %zu smaller than one image", img_stride);
+    if (row_stride % esz || (nimg > 1 && img_stride % esz) || reinterpret_cast<uintptr_t>(out) % esz)
+        return fail(ctx, SM_E_ARG, "png decode: the output is not aligned to its %zu-byte samples", esz);
+    a.nimg = nimg, a.H = H, a.W = W, a.file_ch = fch, a.depth = fdepth, a.bpp = fch * fdepth / 8;
+    const uint64_t rowbytes = (uint64_t)W * a.bpp, stream = (rowbytes + 1) * (uint64_t)H;
+    if (stream >= (1ull << 31))
+        return fail(ctx, SM_E_UNSUPPORTED, "png decode: a filtered stream of %llu bytes (2^31 and more)", (unsigned long long)stream);
+    a.rowbytes = (uint32_t)rowbytes, a.stream_len = stream, a.stream_stride = (stream + 15) & ~15ull;
+    a.nseg = (uint32_t)((stream + smk::PNG_SEG - 1) / smk::PNG_SEG);
+    a.maxpar = 2u * (uint32_t)((stream + smk::PNGDEC_CAP - 1) / smk::PNGDEC_CAP) + 4u;
+    a.out = static_cast<uint8_t*>(const_cast<void*>(out)), a.img_stride = img_stride, a.row_stride = row_stride;
+    return SM_OK;
+}
+
+}  // namespace
+
+const char* sm_pngdec_status_message(int status) { return smk::pngdec_message(status); }
+
+int sm_pngdec_status_code(int status) { return pngdec_code(status); }
+
+int sm_png_info(const uint8_t* file, size_t nbytes, int* H, int* W, int* channels, int* depth)
+{
+    if (!file || !H || !W || !channels || !depth) return fail(nullptr, SM_E_ARG, "png info: a required pointer is NULL");
+    smk::PdHdr h{};
+    const int st = pngdec_info(file, nbytes, h);
+    if (st) return pngdec_fail(nullptr, st, -1);
+    *H = (int)h.H, *W = (int)h.W, *channels = h.channels, *depth = h.depth;
+    return SM_OK;
+}
+
+int sm_png_decode_batch_device(sm_ctx* ctx, const uint8_t* d_files, const uint64_t* d_offsets, const uint64_t* d_sizes,
+                               int nimg, int H, int W, const sm_pngdec_params* p, void* d_out, size_t img_stride_bytes,
+                               size_t row_stride_bytes, int* d_status)
+{
+    if (!ctx) return fail(nullptr, SM_E_ARG, "ctx is NULL");
+    if (!d_files || !d_offsets || !d_sizes || !d_status) return fail(ctx, SM_E_ARG, "png decode: a required pointer is NULL");
+    smk::PdArgs a;
+    int rc;
+    if ((rc = pngdec_setup(ctx, nimg, H, W, p, p ? p->file_channels : 0, p ? p->file_depth : 0, d_out, img_stride_bytes,
+                           row_stride_bytes, a)) != SM_OK)
+        return rc;
+    if (p->max_chunks < 0) return fail(ctx, SM_E_ARG, "png decode: max_chunks %d", p->max_chunks);
+    a.files = d_files, a.offsets = d_offsets, a.sizes = d_sizes;
+    a.max_chunks = p->max_chunks ? (uint32_t)p->max_chunks : 2u * a.nseg + 64u;
+    a.max_file = p->max_file_bytes ? p->max_file_bytes : 2ull * png_bound_of(a.stream_len, a.nseg);
+    if (a.max_file > 0xFFFFFFFFull) a.max_file = 0xFFFFFFFFull;
+    a.zstride = (a.max_file + 15) & ~15ull;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t n = (size_t)nimg;
+    if ((rc = ensure(ctx, ctx->pd_img, n * sizeof(smk::PdImg))) != SM_OK) return rc;
+    if ((rc = ensure(ctx, ctx->pd_chunks, n * a.max_chunks * sizeof(smk::PdChunk))) != SM_OK) return rc;
+    if ((rc = ensure(ctx, ctx->pd_idat, n * a.max_chunks * sizeof(smk::PdIdat))) != SM_OK) return rc;
+    if ((rc = ensure(ctx, ctx->pd_cinfo, n * a.maxpar * sizeof(smk::PdChunkInfo))) != SM_OK) return rc;
+    if ((rc = ensure(ctx, ctx->pd_slots, n * a.maxpar * smk::PNGDEC_CAP)) != SM_OK) return rc;
+    if ((rc = ensure(ctx, ctx->pd_zbuf, n * a.zstride)) != SM_OK) return rc;
+    if ((rc = ensure(ctx, ctx->pd_stream, n * a.stream_stride)) != SM_OK) return rc;
+    if ((rc = ensure(ctx, ctx->pd_seg, n * a.nseg * sizeof(smk::PdChunkInfo))) != SM_OK) return rc;
+    const uint32_t ngrp = (uint32_t)((H + 63) / 64);  // row groups of the unfilter pass
+    if ((rc = ensure(ctx, ctx->pd_carry, n * ngrp * (size_t)W * 4)) != SM_OK) return rc;
+    a.img = (smk::PdImg*)ctx->pd_img.p, a.chunks = (smk::PdChunk*)ctx->pd_chunks.p, a.idat = (smk::PdIdat*)ctx->pd_idat.p;
+    a.cinfo = (smk::PdChunkInfo*)ctx->pd_cinfo.p, a.slots = (uint8_t*)ctx->pd_slots.p, a.zbuf = (uint8_t*)ctx->pd_zbuf.p;
+    a.stream = (uint8_t*)ctx->pd_stream.p, a.seg = (smk::PdChunkInfo*)ctx->pd_seg.p, a.carry = (uint32_t*)ctx->pd_carry.p;
+    const dim3 blk(smk::PNGDEC_BLOCK), wave(64);
+    const uint32_t cgrid = std::min<uint32_t>(a.max_chunks, 256u);
+    hipLaunchKernelGGL(smk::k_pngdec_parse, dim3(nimg), wave, 0, ctx->stream, a);
+    hipLaunchKernelGGL(smk::k_pngdec_crc, dim3(cgrid, nimg), blk, 0, ctx->stream, a);
+    hipLaunchKernelGGL(smk::k_pngdec_inflate, dim3(a.maxpar, nimg), wave, 0, ctx->stream, a);
+    hipLaunchKernelGGL(smk::k_pngdec_place, dim3(nimg), wave, 0, ctx->stream, a);
+    hipLaunchKernelGGL(smk::k_pngdec_compact, dim3(a.maxpar, nimg), blk, 0, ctx->stream, a);
+    hipLaunchKernelGGL(smk::k_pngdec_gather, dim3(cgrid, nimg), blk, 0, ctx->stream, a);
+    hipLaunchKernelGGL(smk::k_pngdec_inflate_serial, dim3(nimg), wave, 0, ctx->stream, a);
+    hipLaunchKernelGGL(smk::k_pngdec_adler, dim3(a.nseg, nimg), blk, 0, ctx->stream, a);
+    hipLaunchKernelGGL(smk::k_pngdec_verify, dim3(nimg), wave, 0, ctx->stream, a);
+    hipLaunchKernelGGL(smk::k_pngdec_unfilter, dim3(ngrp, nimg), blk, 0, ctx->stream, a);
+    hipLaunchKernelGGL(smk::k_pngdec_status, dim3((nimg + 255) / 256), blk, 0, ctx->stream, a, d_status);
+    HIP_TRY(ctx, hipGetLastError());
+    ctx->pd_last_nimg = nimg;
+    return SM_OK;
+}
+
+int sm_png_decode(sm_ctx* ctx, const uint8_t* file, size_t nbytes, const sm_pngdec_params* p, void* out,
+                  size_t row_stride_bytes, int* status)
+{
+    if (!ctx) return fail(nullptr, SM_E_ARG, "ctx is NULL");
+    if (!file || !p || !out) return fail(ctx, SM_E_ARG, "png decode: a required pointer is NULL");
+    if (status) *status = 0;
+    smk::PdHdr h{};
+    int st = pngdec_info(file, nbytes, h);
+    if (st) {
+        if (status) *status = st;
+        return pngdec_fail(ctx, st, -1);
+    }
+    sm_pngdec_params q = *p;
+    if (!q.file_channels) q.file_channels = h.channels;
+    if (!q.file_depth) q.file_depth = h.depth;
+    {  // the chunks the walk on the device can meet: counted here, every length checked first
+        size_t pos = 8, nc = 0;
+        while (nbytes - pos >= 12) {
+            const uint32_t len = smk::pd_be32(file + pos);
+            ++nc;
+            if ((uint64_t)len > nbytes - pos - 12) break;
+            pos += 12 + (size_t)len;
+        }
+        q.max_chunks = (int)std::min<size_t>(nc + 1, 0x7FFFFFFF);
+    }
+    q.max_file_bytes = nbytes;
+    smk::PdArgs a;
+    int rc;
+    if ((rc = pngdec_setup(ctx, 1, (int)h.H, (int)h.W, &q, q.file_channels, q.file_depth, out, 0, row_stride_bytes, a)) != SM_OK)
+        return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t opb = a.kind == SM_PNGDEC_U8 ? (size_t)a.out_ch : a.kind == SM_PNGDEC_DISP_F32 ? 4 : 2;
+    const size_t drow = (size_t)h.W * opb;
+    if ((rc = ensure(ctx, ctx->pd_in, nbytes)) != SM_OK) return rc;
+    if ((rc = ensure(ctx, ctx->pd_tab, 16)) != SM_OK) return rc;
+    if ((rc = ensure(ctx, ctx->pd_out, drow * h.H)) != SM_OK) return rc;
+    if ((rc = ensure(ctx, ctx->pd_status, 4)) != SM_OK) return rc;
+    const uint64_t tab[2] = {0, (uint64_t)nbytes};
+    {
+        StageTimer t_(ctx, ctx->stream, SM_STAGE_H2D, 1);
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->pd_in.p, file, nbytes, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->pd_tab.p, tab, 16, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // tab lives on this frame
+    }
+    const uint64_t* dtab = (const uint64_t*)ctx->pd_tab.p;
+    if ((rc = sm_png_decode_batch_device(ctx, (const uint8_t*)ctx->pd_in.p, dtab, dtab + 1, 1, (int)h.H, (int)h.W, &q,
+                                         ctx->pd_out.p, 0, drow, (int*)ctx->pd_status.p)) != SM_OK)
+        return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(&st, ctx->pd_status.p, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (status) *status = st;
+    if (st) return pngdec_fail(ctx, st, -1);
+    {
+        StageTimer t_(ctx, ctx->stream, SM_STAGE_D2H, 1);
+        HIP_TRY(ctx, hipMemcpy2DAsync(out, row_stride_bytes, ctx->pd_out.p, drow, drow, h.H, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return SM_OK;
+}
+
+int sm_png_decode_host(const uint8_t* file, size_t nbytes, const sm_pngdec_params* p, void* out, size_t row_stride_bytes,
+                       int* status)
+{
+    if (!file || !p || !out) return fail(nullptr, SM_E_ARG, "png decode: a required pointer is NULL");
+    if (status) *status = 0;
+    g_pd_host_path[0] = g_pd_host_path[1] = 0;
+    smk::PdHdr h{};
+    int st = pngdec_info(file, nbytes, h);
+    if (!st) {
+        const int fch = p->file_channels ? p->file_channels : h.channels, fdepth = p->file_depth ? p->file_depth : h.depth;
+        smk::PdArgs a;
+        int rc;
+        if ((rc = pngdec_setup(nullptr, 1, (int)h.H, (int)h.W, p, fch, fdepth, out, 0, row_stride_bytes, a)) != SM_OK) return rc;
+        const uint64_t off = 0, size = nbytes;
+        a.files = file, a.offsets = &off, a.sizes = &size;
+        uint32_t path = 0;
+        st = smk::pngdec_host(a, path);
+        if (path == smk::PD_PATH_PARALLEL) g_pd_host_path[0] = 1;
+        if (path == smk::PD_PATH_SERIAL) g_pd_host_path[1] = 1;
+    }
+    if (status) *status = st;
+    return st ? pngdec_fail(nullptr, st, -1) : SM_OK;
+}
+
+int sm_png_decode_stats(sm_ctx* ctx, int* n_parallel, int* n_serial)
+{
+    if (!n_parallel || !n_serial) return fail(ctx, SM_E_ARG, "png decode: a required pointer is NULL");
+    *n_parallel = *n_serial = 0;
+    if (!ctx) {
+        *n_parallel = g_pd_host_path[0], *n_serial = g_pd_host_path[1];
+        return SM_OK;
+    }
+    if (ctx->pd_last_nimg <= 0) return SM_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    std::vector<smk::PdImg> v((size_t)ctx->pd_last_nimg);
+    HIP_TRY(ctx, hipMemcpyAsync(v.data(), ctx->pd_img.p, v.size() * sizeof(smk::PdImg), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    for (const smk::PdImg& im : v) {
+        if (im.path == smk::PD_PATH_PARALLEL) ++*n_parallel;
+        if (im.path == smk::PD_PATH_SERIAL) ++*n_serial;
+    }
     return SM_OK;
 }
 

@@ -147,6 +147,18 @@ SM_HD uint32_t png_filt(int type, uint32_t x, uint32_t a, uint32_t b, uint32_t c
     return (x - pred) & 255u;
 }
 
+// the bits of v in reverse order
+SM_HD uint32_t png_bitrev32(uint32_t v)
+{
+#if defined(__clang__)
+    return __builtin_bitreverse32(v);
+#else
+    uint32_t r = 0;
+    for (int i = 0; i < 32; ++i) r |= ((v >> i) & 1u) << (31 - i);
+    return r;
+#endif
+}
+
 SM_HD uint32_t png_mag(uint32_t f) { return f < 128u ? f : 256u - f; }
 
 // the type with the smallest sum, ties to the lowest type
@@ -325,7 +337,7 @@ SM_HD uint32_t png_code_of(const uint8_t* len, const uint32_t* blc, int s)
     uint32_t c = 0;
     for (uint32_t b = 2; b <= l; ++b) c = (c + blc[b - 1]) << 1;
     for (int t = 0; t < s; ++t) c += len[t] == l ? 1u : 0u;
-    return __builtin_bitreverse32(c) >> (32u - l);
+    return png_bitrev32(c) >> (32u - l);
 }
 
 inline void png_huff_build_host(const uint32_t* freq, int nsym, int maxbits, uint8_t* len, uint16_t* code, PngHuffWork& w)
@@ -759,7 +771,8 @@ inline void png_encode_host(const PngArgs& s, std::vector<uint8_t>& file)
 }
 
 // ---------------------------------------------------------------------------------------------
-// kernels
+// kernels (left out when a host compiler reads this header for the CPU twins alone)
+#if defined(__HIPCC__)
 
 // per image the minimum of d and of -d of an int16 map: keys[img][2], initialised to INT_MAX
 __global__ void __launch_bounds__(PNG_BLOCK) k_png_minmax(PngArgs a, int* keys)
@@ -1160,5 +1173,7 @@ __global__ void __launch_bounds__(PNG_BLOCK) k_png_scatter(PngArgs a)
     for (uint32_t i = tid; i < v.nbytes; i += PNG_BLOCK)
         if (at + 8 + i < cap) o[at + 8 + i] = slot[i];
 }
+
+#endif  // __HIPCC__
 
 }  // namespace smk

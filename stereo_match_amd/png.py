@@ -11,6 +11,15 @@ where the images already are:
   inside the filter kernel;
 * :func:`imencode_png_host` — the same file from the same functions on the CPU.
 
+PNG input, decoded on the device (``sm_png_decode*``):
+
+* :func:`imread`, :func:`imdecode` — ``cv2.imread`` / ``cv2.imdecode`` for PNG files with flags
+  ``1``, ``0`` and ``-1``, as a numpy array or (``as_tensor=True``) a CUDA tensor;
+  :func:`imdecode_batch` for files of one geometry in one call;
+* :func:`read_disparity_png`, :func:`decode_disparity_png` — a KITTI 16-bit map back to int16 x16
+  or float32 disparities;
+* :func:`imdecode_host` — the same pixels from the same functions on the CPU.
+
 The files are standard PNGs (one IDAT chunk per 32 KiB of the filtered stream); the filter choice
 and the coder are the package's own and documented in ``include/stereo_match_amd.h``.  The integer
 rounding of the min-max picture is this package's contract: OpenCV's ``normalize`` is not pinned.
@@ -201,3 +210,161 @@ def write_disparity_png(filename, disp, fmt="kitti", lo=None, hi=None, *, device
     with open(filename, "wb") as f:
         f.write(data)
     return True
+
+
+# ---- PNG input ---------------------------------------------------------------
+def _file_bytes(buf) -> np.ndarray:
+    if _is_torch(buf):
+        buf = buf.cpu().numpy()
+    b = np.frombuffer(buf, np.uint8) if not isinstance(buf, np.ndarray) else np.ascontiguousarray(buf, np.uint8).reshape(-1)
+    return b
+
+
+def _dec_params(info, flags, keep_channel_order=False, disp=None, invalid=None):
+    """(sm_pngdec_params, output shape, numpy dtype) for a file of geometry ``info``."""
+    H, W, ch, depth = info
+    p = _lib.SmPngDecParams()
+    p.file_channels, p.file_depth = ch, depth
+    p.keep_channel_order = int(bool(keep_channel_order))
+    if disp is not None:
+        dt = np.dtype(disp)
+        if dt == np.int16:
+            p.out_kind, p.invalid_i16 = _lib.SM_PNGDEC_DISP_I16, int(-16 if invalid is None else invalid)
+        elif dt == np.float32:
+            p.out_kind, p.invalid_f32 = _lib.SM_PNGDEC_DISP_F32, float(-1.0 if invalid is None else invalid)
+        else:
+            raise ValueError(f"dtype must be int16 (x16) or float32, not {dt}")
+        p.flags, p.disp_mode = -1, _lib.SM_PNG_DISP_KITTI
+        return p, (H, W), dt
+    flags = int(flags)
+    if flags not in (1, 0, -1):
+        raise ValueError(f"flags must be 1 (BGR), 0 (gray) or -1 (unchanged), not {flags}")
+    p.flags = flags
+    if flags == -1 and depth == 16:
+        p.out_kind = _lib.SM_PNGDEC_U16
+        return p, (H, W), np.dtype(np.uint16)
+    p.out_kind = _lib.SM_PNGDEC_U8
+    three = flags == 1 or (flags == -1 and ch >= 3)
+    return p, ((H, W, 3) if three else (H, W)), np.dtype(np.uint8)
+
+
+def _torch_dtype(dt):
+    import torch
+
+    return {"uint8": torch.uint8, "uint16": torch.uint16, "int16": torch.int16, "float32": torch.float32}[np.dtype(dt).name]
+
+
+def _decode_batch_device(bufs, flags, device, keep_channel_order=False, disp=None, invalid=None):
+    """The files ``bufs`` (equal geometry) on the device: a CUDA tensor [N, ...]."""
+    import torch
+
+    files = [_file_bytes(b) for b in bufs]
+    if not files:
+        raise ValueError("empty batch")
+    info = None
+    for i, f in enumerate(files):
+        try:
+            g = _lib.png_info(f)
+        except _lib.SmError as e:
+            raise _lib.SmError(e.code, f"image {i}: {e.args[0]}") from None
+        if info is None:
+            info = g
+        elif g != info:
+            _unsupported(f"image {i}: geometry {g} differs from image 0's {info} (H, W, channels, depth)")
+    prm, shape, dt = _dec_params(info, flags, keep_channel_order, disp, invalid)
+    H, W = info[:2]
+    dev = torch.device("cuda", int(device))
+    eng = _lib.engine(dev.index)
+    eng.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+    offs, at = [], 0
+    for f in files:
+        offs.append(at)
+        at += (f.size + 15) & ~15
+    blob = torch.empty(max(at, 16), dtype=torch.uint8, pin_memory=True)
+    hb = blob.numpy()
+    for f, o in zip(files, offs):
+        hb[o:o + f.size] = f
+    tab = torch.tensor([offs, [f.size for f in files]], dtype=torch.int64).pin_memory()
+    d_blob = blob.to(dev, non_blocking=True)
+    d_tab = tab.to(dev, non_blocking=True)
+    n = len(files)
+    out = torch.empty((n,) + shape, dtype=_torch_dtype(dt), device=dev)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    prm.max_chunks = max(f.size for f in files) // 12 + 1
+    prm.max_file_bytes = max(f.size for f in files)
+    eng.png_decode_batch_device(d_blob.data_ptr(), d_tab[0].data_ptr(), d_tab[1].data_ptr(), n, H, W, prm,
+                                out.data_ptr(), out.stride(0) * out.element_size(), out.stride(1) * out.element_size(),
+                                status.data_ptr())
+    st = status.cpu().tolist()  # synchronises: the pinned staging buffers are free again
+    for i, code in enumerate(st):
+        if code:
+            lib = _lib.load()
+            raise _lib.SmError(lib.sm_pngdec_status_code(code),
+                               f"png decode: image {i}: {lib.sm_pngdec_status_message(code).decode()}")
+    return out
+
+
+def imdecode_batch(bufs, flags=1, *, device=0, keep_channel_order=False):
+    """PNG files of one geometry (a sequence of bytes-like objects) decoded in one call: a CUDA
+    tensor ``[N, H, W]`` or ``[N, H, W, 3]`` (``flags`` as in :func:`imdecode`).  A corrupt or
+    unsupported file raises ``SmError`` naming its index."""
+    return _decode_batch_device(list(bufs), flags, device, keep_channel_order)
+
+
+def imdecode(buf, flags=1, *, device=0, as_tensor=False, keep_channel_order=False):
+    """``cv2.imdecode(buf, flags)`` for a PNG file in memory (bytes, bytearray, a uint8 array).
+
+    ``flags=1``: BGR uint8 ``[H, W, 3]`` (a gray file replicated, 16-bit samples ``>> 8``, alpha
+    dropped; ``keep_channel_order`` leaves the file's RGB).  ``flags=0``: gray uint8 ``[H, W]``; a
+    colour file goes through this package's ``bgr2gray`` formula
+    ``(1868*B + 9617*G + 4899*R + 8192) >> 14`` -- OpenCV converts inside its decoder and does not
+    pin that rounding, so a colour file read with ``flags=0`` may differ from cv2 by one level.
+    ``flags=-1``: the file's own channels and depth without alpha (uint16 ``[H, W]`` for a 16-bit
+    file).  Returns a numpy array, or with ``as_tensor=True`` a CUDA tensor that stays on the device.
+    A corrupt or unsupported file raises ``SmError``."""
+    if as_tensor:
+        return _decode_batch_device([buf], flags, device, keep_channel_order)[0]
+    f = _file_bytes(buf)
+    prm, shape, dt = _dec_params(_lib.png_info(f), flags, keep_channel_order)
+    return _lib.engine(device).png_decode(f, prm, np.empty(shape, dt))
+
+
+def imdecode_host(buf, flags=1, *, keep_channel_order=False):
+    """:func:`imdecode` on the CPU (``sm_png_decode_host``): the same pixels, no device."""
+    f = _file_bytes(buf)
+    prm, shape, dt = _dec_params(_lib.png_info(f), flags, keep_channel_order)
+    return _lib.png_decode_host(f, prm, np.empty(shape, dt))
+
+
+def imread(filename, flags=1, *, device=0, as_tensor=False):
+    """``cv2.imread(filename, flags)`` for PNG files (see :func:`imdecode`).  A file that cannot be
+    opened gives ``None``, as cv2 does; a corrupt or unsupported one raises ``SmError``."""
+    try:
+        with open(filename, "rb") as f:
+            data = f.read()
+    except OSError:
+        return None
+    return imdecode(data, flags, device=device, as_tensor=as_tensor)
+
+
+def decode_disparity_png(buf, fmt="kitti", dtype=np.int16, invalid=None, *, device=0, as_tensor=False, host=False):
+    """A KITTI disparity PNG (16-bit gray, value = disparity * 256, 0 = invalid) back to a map:
+    ``dtype=np.int16`` gives the x16 fixed point ``v >> 4`` (exact for what
+    :func:`encode_disparity_png` wrote from an int16 map), ``np.float32`` gives ``v / 256``; a 0
+    sample becomes ``invalid`` (default -16, one pixel below zero as the matcher's invalid, and
+    -1.0).  ``host=True`` decodes on the CPU."""
+    if fmt != "kitti":
+        raise ValueError(f"only fmt='kitti' maps are read back, not {fmt!r}")
+    if as_tensor and not host:
+        return _decode_batch_device([buf], -1, device, False, dtype, invalid)[0]
+    f = _file_bytes(buf)
+    prm, shape, dt = _dec_params(_lib.png_info(f), -1, False, dtype, invalid)
+    out = np.empty(shape, dt)
+    return _lib.png_decode_host(f, prm, out) if host else _lib.engine(device).png_decode(f, prm, out)
+
+
+def read_disparity_png(filename, fmt="kitti", dtype=np.int16, invalid=None, *, device=0, as_tensor=False):
+    """:func:`decode_disparity_png` of a file."""
+    with open(filename, "rb") as f:
+        data = f.read()
+    return decode_disparity_png(data, fmt, dtype, invalid, device=device, as_tensor=as_tensor)
