@@ -504,6 +504,65 @@ int sm_png_decode_stats(sm_ctx* ctx, int* n_parallel, int* n_serial);
 const char* sm_pngdec_status_message(int status);
 int sm_pngdec_status_code(int status);
 
+/* ---- JPEG input: cv2.imread(".jpg") of the reference's production flow
+ * (build_npz.py:229, io_functions.py:92, try_try.py:56-57), decoded on the device with
+ * libjpeg-turbo's default arithmetic (islow IDCT, fancy upsampling, jdcolor's tables) restated bit
+ * for bit.
+ *
+ * Files: baseline sequential Huffman (SOF0, or SOF1 at 8 bits), one interleaved scan, 1 component
+ * or 3 that libjpeg's rule reads as YCbCr, sampling 4:4:4, 4:2:2 (luma 2x1) or 4:2:0 (luma 2x2),
+ * with or without restart markers; APPn / COM are skipped and the EXIF orientation is not
+ * applied.  Progressive, lossless or arithmetic coding, 12-bit precision, several scans, other
+ * sampling factors, 4 components, Adobe RGB and DNL are SM_E_UNSUPPORTED with a message that names
+ * the reason.  Anything else that does not decode (truncated, a code in no table, a coefficient
+ * index past 63, restart markers missing or out of sequence, data left over, a wrong segment
+ * length) is SM_E_DATA; libjpeg warns and returns a picture for some of these, this package
+ * refuses them.
+ * Output by flags (cv2.imread's): 1 -> BGR uint8 [H][W][3] (a gray file replicated; RGB order with
+ * keep_channel_order), 0 -> the Y plane uint8 [H][W] (chroma is never transformed, as libjpeg
+ * does for JCS_GRAYSCALE), -1 -> gray for a gray file, BGR for a colour file. */
+typedef struct sm_jpegdec_params {
+    int flags;               /* 1, 0, -1 as cv2.imread */
+    int keep_channel_order;  /* 3-channel output: 0 gives BGR, 1 RGB */
+    int file_channels;       /* of the files: 1 or 3; 0: taken from the file (host-pointer calls) */
+    int subsampling;         /* of the files: 0 (gray), 444, 422 or 420; ignored when file_channels is 0 */
+    uint64_t max_file_bytes; /* batch: bytes a file may have (sizes the work buffers) */
+    const void* d_desc;      /* batch: nimg descriptors of sm_jpeg_parse in device memory,
+                                sm_jpeg_desc_bytes() apart */
+} sm_jpegdec_params;
+
+/* Frame header of a JPEG file in host memory: *channels 1 or 3, *subsampling 0 (gray), 444, 422 or
+ * 420.  SM_E_DATA for bytes that are no JPEG file, SM_E_UNSUPPORTED for a file this package does
+ * not decode.  Host only, no context. */
+int sm_jpeg_info(const uint8_t* file, size_t nbytes, int* H, int* W, int* channels, int* subsampling);
+/* The descriptor the device decodes from (geometry, tables, the scan's byte range), parsed on the
+ * host from the segments before the scan: sm_jpeg_desc_bytes() bytes at desc.  *status (may be
+ * NULL) gets the decoder's status code.  Host only, no context. */
+size_t sm_jpeg_desc_bytes(void);
+int sm_jpeg_parse(const uint8_t* file, size_t nbytes, void* desc, int* status);
+/* nimg files of one geometry (H, W, p->file_channels, p->subsampling) in device memory, file i at
+ * d_files + d_offsets[i] with d_sizes[i] bytes and its descriptor at p->d_desc: image i to
+ * d_out + i*img_stride_bytes, rows row_stride_bytes apart.  d_status[i]: 0, or a positive code of
+ * the first fault found in file i (sm_jpegdec_status_message); the pixels of such an image are
+ * undefined.  Asynchronous. */
+int sm_jpeg_decode_batch_device(sm_ctx* ctx, const uint8_t* d_files, const uint64_t* d_offsets, const uint64_t* d_sizes,
+                                int nimg, int H, int W, const sm_jpegdec_params* p, void* d_out, size_t img_stride_bytes,
+                                size_t row_stride_bytes, int* d_status);
+/* One file on host pointers.  A faulty file is SM_E_DATA or SM_E_UNSUPPORTED with the message of
+ * its status; *status (may be NULL) gets the code.  Synchronous. */
+int sm_jpeg_decode(sm_ctx* ctx, const uint8_t* file, size_t nbytes, const sm_jpegdec_params* p, void* out,
+                   size_t row_stride_bytes, int* status);
+/* The same pixels and status from a plain serial decoder built from the same functions, on the
+ * CPU: its verdict is the reference.  Needs no context and no device. */
+int sm_jpeg_decode_host(const uint8_t* file, size_t nbytes, const sm_jpegdec_params* p, void* out,
+                        size_t row_stride_bytes, int* status);
+/* Of the last decode call: the sub-sequences (lanes) its entropy decode used, summed over the
+ * images, and the largest number of synchronisation rounds an image needed (ctx NULL: the lanes
+ * the last sm_jpeg_decode_host of this thread would have used, and 0).  Synchronises the stream. */
+int sm_jpeg_decode_stats(sm_ctx* ctx, int* n_subsequences, int* n_sync_rounds);
+const char* sm_jpegdec_status_message(int status);
+int sm_jpegdec_status_code(int status);
+
 /* ---- StereoBM (the reference's method="BM" branch,
  * stereo_vision/stereo_vision.py:164-166: cv2.StereoBM_create(numDisparities,
  * blockSize)).  Fields follow cv::StereoBM's setters. */

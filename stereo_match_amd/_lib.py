@@ -90,6 +90,13 @@ class SmPngDecParams(ctypes.Structure):
                 ("max_file_bytes", ctypes.c_uint64)]
 
 
+class SmJpegDecParams(ctypes.Structure):
+    """Mirror of ``struct sm_jpegdec_params`` (JPEG input: imread flags, the files' geometry, the
+    batch's file-size bound and device descriptors)."""
+    _fields_ = [("flags", ctypes.c_int), ("keep_channel_order", ctypes.c_int), ("file_channels", ctypes.c_int),
+                ("subsampling", ctypes.c_int), ("max_file_bytes", ctypes.c_uint64), ("d_desc", ctypes.c_void_p)]
+
+
 SM_PNG_SEG = 32768
 SM_PNGDEC_CAP = 32768
 SM_PNGDEC_U8, SM_PNGDEC_U16, SM_PNGDEC_DISP_I16, SM_PNGDEC_DISP_F32 = 0, 1, 2, 3
@@ -212,6 +219,20 @@ _SIGS = {
     "sm_png_decode_stats": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_int), _c.POINTER(_c.c_int)]),
     "sm_pngdec_status_message": (_c.c_char_p, [_c.c_int]),
     "sm_pngdec_status_code": (_c.c_int, [_c.c_int]),
+    "sm_jpeg_info": (_c.c_int, [_c.c_void_p, _c.c_size_t, _c.POINTER(_c.c_int), _c.POINTER(_c.c_int),
+                                _c.POINTER(_c.c_int), _c.POINTER(_c.c_int)]),
+    "sm_jpeg_desc_bytes": (_c.c_size_t, []),
+    "sm_jpeg_parse": (_c.c_int, [_c.c_void_p, _c.c_size_t, _c.c_void_p, _c.POINTER(_c.c_int)]),
+    "sm_jpeg_decode_batch_device": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int,
+                                               _c.c_int, _c.POINTER(SmJpegDecParams), _c.c_void_p, _c.c_size_t,
+                                               _c.c_size_t, _c.c_void_p]),
+    "sm_jpeg_decode": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_size_t, _c.POINTER(SmJpegDecParams), _c.c_void_p,
+                                  _c.c_size_t, _c.POINTER(_c.c_int)]),
+    "sm_jpeg_decode_host": (_c.c_int, [_c.c_void_p, _c.c_size_t, _c.POINTER(SmJpegDecParams), _c.c_void_p, _c.c_size_t,
+                                       _c.POINTER(_c.c_int)]),
+    "sm_jpeg_decode_stats": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_int), _c.POINTER(_c.c_int)]),
+    "sm_jpegdec_status_message": (_c.c_char_p, [_c.c_int]),
+    "sm_jpegdec_status_code": (_c.c_int, [_c.c_int]),
     "sm_bm_default_params": (_c.c_int, [_c.c_int, _c.c_int, _c.POINTER(SmBmParams)]),
     "sm_bm_right_matcher_params": (_c.c_int, [_c.POINTER(SmBmParams), _c.POINTER(SmBmParams)]),
     "sm_bm_compute": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int,
@@ -327,6 +348,59 @@ def png_decode_host(buf, prm: "SmPngDecParams", out: np.ndarray):
     functions the GPU kernels run.  Needs no context and no device."""
     b = np.frombuffer(buf, np.uint8)
     rc = load().sm_png_decode_host(b.ctypes.data, b.size, ctypes.byref(prm), out.ctypes.data, out.strides[0], None)
+    if rc != SM_OK:
+        _raise(rc, None)
+    return out
+
+
+def _file_ptr(b: np.ndarray) -> int:
+    return b.ctypes.data if b.size else np.zeros(1, np.uint8).ctypes.data
+
+
+def jpeg_info(buf):
+    """sm_jpeg_info: (H, W, channels, subsampling) of a JPEG file held in a bytes-like object;
+    subsampling 0 (gray), 444, 422 or 420.  Host only."""
+    b = np.frombuffer(buf, np.uint8)
+    v = [ctypes.c_int() for _ in range(4)]
+    rc = load().sm_jpeg_info(_file_ptr(b), b.size, *[ctypes.byref(x) for x in v])
+    if rc != SM_OK:
+        _raise(rc, None)
+    return tuple(x.value for x in v)
+
+
+def jpeg_parse(buf) -> np.ndarray:
+    """sm_jpeg_parse: the descriptor the device decodes a file from, as a uint8 array.  Host only."""
+    lib = load()
+    b = np.frombuffer(buf, np.uint8)
+    desc = np.zeros(lib.sm_jpeg_desc_bytes(), np.uint8)
+    rc = lib.sm_jpeg_parse(_file_ptr(b), b.size, desc.ctypes.data, None)
+    if rc != SM_OK:
+        _raise(rc, None)
+    return desc
+
+
+def jpeg_desc_info(desc: np.ndarray):
+    """(H, W, channels, subsampling) from a descriptor of :func:`jpeg_parse` (the leading words of
+    csrc/sm_jpegdec.hpp's JdDesc: status, W, H, components, luma factors h and v)."""
+    _, W, H, nc, hs, vs = (int(x) for x in desc[:24].view(np.int32))
+    return H, W, nc, (0 if nc == 1 else 444 if hs == 1 else 422 if vs == 1 else 420)
+
+
+def jpeg_decode_stats(ctx=None):
+    """sm_jpeg_decode_stats: (sub-sequences, synchronisation rounds) of the last decode call of this
+    context, or (ctx None) of this thread's last sm_jpeg_decode_host."""
+    a, b = ctypes.c_int(), ctypes.c_int()
+    rc = load().sm_jpeg_decode_stats(ctx, ctypes.byref(a), ctypes.byref(b))
+    if rc != SM_OK:
+        _raise(rc, ctx)
+    return a.value, b.value
+
+
+def jpeg_decode_host(buf, prm: "SmJpegDecParams", out: np.ndarray):
+    """sm_jpeg_decode_host into ``out`` (rows ``out.strides[0]`` apart): the plain serial decoder on
+    the CPU, built from the functions the GPU kernels run.  Needs no context and no device."""
+    b = np.frombuffer(buf, np.uint8)
+    rc = load().sm_jpeg_decode_host(_file_ptr(b), b.size, ctypes.byref(prm), out.ctypes.data, out.strides[0], None)
     if rc != SM_OK:
         _raise(rc, None)
     return out
@@ -739,6 +813,22 @@ class Engine:
                                 prm: "SmPngDecParams", d_out: int, img_stride: int, row_stride: int, d_status: int):
         self._check(self._lib.sm_png_decode_batch_device(self.ctx, d_files, d_offsets, d_sizes, nimg, H, W,
                                                          ctypes.byref(prm), d_out, img_stride, row_stride, d_status))
+
+    def jpeg_decode(self, buf, prm: "SmJpegDecParams", out: np.ndarray) -> np.ndarray:
+        """sm_jpeg_decode: one file in host memory into the host array ``out`` (decoded on the device)."""
+        b = np.frombuffer(buf, np.uint8)
+        self._check(self._lib.sm_jpeg_decode(self.ctx, _file_ptr(b), b.size, ctypes.byref(prm), out.ctypes.data,
+                                             out.strides[0], None))
+        return out
+
+    def jpeg_decode_batch_device(self, d_files: int, d_offsets: int, d_sizes: int, nimg: int, H: int, W: int,
+                                 prm: "SmJpegDecParams", d_out: int, img_stride: int, row_stride: int, d_status: int):
+        self._check(self._lib.sm_jpeg_decode_batch_device(self.ctx, d_files, d_offsets, d_sizes, nimg, H, W,
+                                                          ctypes.byref(prm), d_out, img_stride, row_stride, d_status))
+
+    def jpeg_decode_stats(self):
+        """(sub-sequences, synchronisation rounds) of this context's last JPEG decode call."""
+        return jpeg_decode_stats(self.ctx)
 
     def png_decode_stats(self):
         """(parallel, serial): the inflate paths of the images of the last decode call."""

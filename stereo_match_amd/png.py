@@ -30,7 +30,7 @@ import os
 
 import numpy as np
 
-from . import _lib
+from . import _lib, jpeg as _jpeg
 
 
 def _is_torch(x) -> bool:
@@ -307,8 +307,12 @@ def _decode_batch_device(bufs, flags, device, keep_channel_order=False, disp=Non
 def imdecode_batch(bufs, flags=1, *, device=0, keep_channel_order=False):
     """PNG files of one geometry (a sequence of bytes-like objects) decoded in one call: a CUDA
     tensor ``[N, H, W]`` or ``[N, H, W, 3]`` (``flags`` as in :func:`imdecode`).  A corrupt or
-    unsupported file raises ``SmError`` naming its index."""
-    return _decode_batch_device(list(bufs), flags, device, keep_channel_order)
+    unsupported file raises ``SmError`` naming its index.  A batch whose first buffer begins
+    ``FF D8 FF`` is a batch of JPEG files (:mod:`.jpeg`)."""
+    bufs = list(bufs)
+    if bufs and _jpeg.is_jpeg(_file_bytes(bufs[0])):
+        return _jpeg.decode_batch_device([_file_bytes(b) for b in bufs], flags, device, keep_channel_order)
+    return _decode_batch_device(bufs, flags, device, keep_channel_order)
 
 
 def imdecode(buf, flags=1, *, device=0, as_tensor=False, keep_channel_order=False):
@@ -321,23 +325,34 @@ def imdecode(buf, flags=1, *, device=0, as_tensor=False, keep_channel_order=Fals
     pin that rounding, so a colour file read with ``flags=0`` may differ from cv2 by one level.
     ``flags=-1``: the file's own channels and depth without alpha (uint16 ``[H, W]`` for a 16-bit
     file).  Returns a numpy array, or with ``as_tensor=True`` a CUDA tensor that stays on the device.
-    A corrupt or unsupported file raises ``SmError``."""
+    A corrupt or unsupported file raises ``SmError``.
+
+    A buffer that begins ``FF D8 FF`` is a baseline JPEG file and gives libjpeg-turbo's pixels
+    (:mod:`.jpeg`): ``flags=0`` is then the file's Y plane, and the EXIF orientation is not applied."""
+    f = _file_bytes(buf)
+    if _jpeg.is_jpeg(f):
+        if as_tensor:
+            return _jpeg.decode_batch_device([f], flags, device, keep_channel_order)[0]
+        return _jpeg.decode(f, flags, device, keep_channel_order)
     if as_tensor:
         return _decode_batch_device([buf], flags, device, keep_channel_order)[0]
-    f = _file_bytes(buf)
     prm, shape, dt = _dec_params(_lib.png_info(f), flags, keep_channel_order)
     return _lib.engine(device).png_decode(f, prm, np.empty(shape, dt))
 
 
 def imdecode_host(buf, flags=1, *, keep_channel_order=False):
-    """:func:`imdecode` on the CPU (``sm_png_decode_host``): the same pixels, no device."""
+    """:func:`imdecode` on the CPU (``sm_png_decode_host``, ``sm_jpeg_decode_host``): the same
+    pixels, no device."""
     f = _file_bytes(buf)
+    if _jpeg.is_jpeg(f):
+        return _jpeg.decode_host(f, flags, keep_channel_order)
     prm, shape, dt = _dec_params(_lib.png_info(f), flags, keep_channel_order)
     return _lib.png_decode_host(f, prm, np.empty(shape, dt))
 
 
 def imread(filename, flags=1, *, device=0, as_tensor=False):
-    """``cv2.imread(filename, flags)`` for PNG files (see :func:`imdecode`).  A file that cannot be
+    """``cv2.imread(filename, flags)`` for PNG and baseline JPEG files (see :func:`imdecode`; the
+    content decides, not the extension).  A file that cannot be
     opened gives ``None``, as cv2 does; a corrupt or unsupported one raises ``SmError``."""
     try:
         with open(filename, "rb") as f:
