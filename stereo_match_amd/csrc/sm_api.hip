@@ -1,4 +1,4 @@
-// sm_api.hip — C-ABI (include/stereo_match_amd.h) around the gfx950 kernels.
+// sm_api.hip — C-ABI (include/stereo_match_amd.h) of the matcher core (leaf subsystems: sm_api_*.hip, sm_ctx.hpp).
 //
 // Host side of the drop-in boundary for stereo_vision/stereo_vision.py:153-179
 // (cv2.StereoSGBM_create(...).compute).  Parameter normalisation mirrors
@@ -25,20 +25,12 @@
 #include <type_traits>
 #include <vector>
 
-#include "../../include/stereo_match_amd.h"
+#include "sm_ctx.hpp"
 #include "sm_cost.hpp"
 #include "sm_paths.hpp"
 #include "sm_post.hpp"
 #include "sm_wls.hpp"
 #include "sm_speckle.hpp"
-#include "sm_reproject.hpp"
-#include "sm_rectify.hpp"
-#include "sm_nlm.hpp"
-#include "sm_filter.hpp"
-#include "sm_cloud.hpp"
-#include "sm_png.hpp"
-#include "sm_pngdec.hpp"
-#include "sm_jpegdec.hpp"
 #include "sm_bm.hpp"
 #include "sm_wide.hpp"
 #include "sm_sweep_host.hpp"
@@ -60,11 +52,6 @@ namespace {
 
 thread_local std::string g_thread_error;
 
-struct DevBuf {
-    void* p = nullptr;
-    size_t n = 0;
-};
-
 struct Norm {
     // D: disparities the kernels run (a multiple of 16); Dv: the caller's numDisparities.
     // They differ only for an external cost volume whose plane count is not a multiple of
@@ -75,21 +62,6 @@ struct Norm {
     int minX1, maxX1, width1, ndirs, dpl;
     int cn;    // input channels (1 gray, 3 BGR)
     bool wide;  // SGBM cost outside the int16-exact range (or BGR): sm_wide.hpp path
-};
-
-struct TimedEvent {
-    int stage, pairs;
-    hipEvent_t a, b;
-};
-
-// per-group device buffers (double-buffered across launch groups)
-struct BufSet {
-    DevBuf census[2], cost, L, raw;
-    DevBuf part, key2, pre;  // sweep engine: u16 partial sums, WTA winner records, sub-pixel inputs
-    DevBuf st;               // in-sweep E/W lines (MODE 3): the strip segments' boundary states
-    DevBuf vst;              // MODE 3 row bands: the vertical paths' boundary states
-    hipEvent_t paths_done = nullptr, wta_done = nullptr;
-    bool pending = false;  // wta_done recorded and not yet waited for by stream A
 };
 
 // the E/W patch pass with atomic corrections where no partial cell can saturate (k_ew_patch ATOM)
@@ -139,97 +111,6 @@ constexpr int kAblationFlags = 1 | 2 | 4 | DBG_STORE_W | DBG_ROW | DBG_SWEEP_V2 
 
 }  // namespace
 
-struct sm_ctx {
-    int device = 0;
-    hipStream_t own_stream = nullptr;
-    hipStream_t stream = nullptr;  // stream A
-    hipStream_t side = nullptr;    // stream B
-    DevBuf img[2], planes, out, dbg, volbuf, sp_parent, sp_count, rp_in, rp_out, rp_min, bm_pre[2], bm_cost;
-    DevBuf rm_src, rm_mapx, rm_mapy, rm_dst, rm_gray;  // host-pointer rectify-map / remap / gray entry points
-    // fastNlMeansDenoising: the non-zero prefix of the weight table on the device, cached for the
-    // (h, t, s) it was built for; its host copy lives here too, so it outlives the upload
-    DevBuf nlm_tab;
-    std::vector<int32_t> nlm_tab_host;
-    uint32_t nlm_key_h = 0;
-    int nlm_key_t = 0, nlm_key_s = 0, nlm_ntab = 0, nlm_shift = 0;
-    // point clouds (sm_cloud.hpp): block totals and their scans of the extraction (cl_) and the
-    // PLY formatter (ply_); vertices, colours and the PLY body of the host and fused entry points
-    DevBuf cl_tot, cl_off, ply_tot, ply_off, cl_verts, cl_colors, cl_out;
-    // PNG output (sm_png.hpp): the filtered streams, the segments' data and records, the chunk
-    // offsets, per-image records, min / max keys; image, files and sizes of the host entry point
-    DevBuf png_stream, png_slots, png_seg, png_off, png_img, png_range, png_in, png_out, png_nb;
-    // PNG input (sm_pngdec.hpp): per-image records, chunk tables, the chunks' slots and records, the
-    // concatenated IDAT data, the filtered streams, Adler pieces, the carried rows; the staged
-    // file, its offset / size pair, the pixels and the status of the host-pointer call
-    DevBuf pd_img, pd_chunks, pd_idat, pd_cinfo, pd_slots, pd_zbuf, pd_stream, pd_seg, pd_carry, pd_in, pd_tab, pd_out,
-        pd_status;
-    int pd_last_nimg = 0;
-    // JPEG input (sm_jpegdec.hpp): per-image records, the restart intervals, the lanes' states and
-    // counts, coefficients, component planes; the staged file, descriptor, offset / size pair,
-    // pixels and status of the host-pointer call
-    DevBuf jd_img, jd_iv, jd_state, jd_lane, jd_coef, jd_planes, jd_in, jd_desc, jd_tab, jd_out, jd_status;
-    int jd_last_nimg = 0;
-    DevBuf flt_a;  // image_measure: the first Gaussian's result, [img][H][W] float64
-    DevBuf wls_num, wls_den, wls_inter, wls_w, wls_disp[2], wls_out;  // WLS scratch
-    DevBuf wls_R, wls_IT;         // WLS: Thomas pivots / elimination factors of every pass
-    hipStream_t wls_stream = nullptr;  // compute_disparity: WLS weights + pivots beside the matchers
-    hipStream_t lr_stream = nullptr;   // compute_disparity: the left matcher, staggered behind the right one
-    hipEvent_t ev_stagger = nullptr;
-    // (set by the caller for one call) recorded on the stream right after a MODE 3 down sweep;
-    // sweep_done_hit tells the caller it was
-    hipEvent_t sweep_done_ev = nullptr;
-    bool sweep_done_hit = false;
-    int tune_lr_stagger = 0;  // SM_TUNE_LR_STAGGER: 0 automatic (on), -1 off
-    hipEvent_t ev_wls_fork = nullptr, ev_wls_ready = nullptr;
-    DevBuf hop, sweep_err;  // sweep engine: strip-boundary granules, device error word
-    DevBuf volwin;          // external cost volumes, automatic window: [pair] min/max keys + offset/scale
-
-    void* pin = nullptr;    // page-locked host staging of the host-pointer entry points (HostStage)
-    size_t pin_n = 0;
-    // compute_disparity: the right matcher runs on a twin context (own streams and
-    // buffers); created on first use, destroyed with this one
-    sm_ctx* twin = nullptr;
-    hipEvent_t ev_lr_fork = nullptr, ev_lr_join = nullptr;
-    std::vector<uint32_t> cu_mask;  // sm_set_cu_mask words (applied to the twin too)
-    uint32_t hop_epoch = 0;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;  // sweep engine: E/W kernel on the side stream
-    hipEvent_t ev_fb_fork = nullptr, ev_fb_join = nullptr;  // sweep engine: fallback beside the LR pass
-    hipEvent_t ev_ew_done = nullptr;  // banded lines: the E/W patch on the side stream (before the WTA)
-    const uint32_t* fb_guard = nullptr;  // set while enqueuing a group's guarded per-direction fallback
-    hipStream_t wta_override = nullptr;  // stream of the WTA launch when it is not stream_b()
-    const uint32_t* wta_skip = nullptr;  // the WTA row kernel exits when this flag is set (WtaArgs::skip)
-    int16_t* wta_dst = nullptr;  // integer WTA index of the current launch group (sm_compute_wta_*), or null
-    BufSet set[2];
-    int next_set = 0;
-    // geometry of the last computation (for sm_debug_fetch): its last pair
-    int lastH = 0, lastW = 0, last_width1 = 0, lastD = 0, last_ndirs = 0, last_cost = 0, last_minD = 0;
-    int last_minX1 = 0, last_index = 0, last_set = 0;
-    size_t last_L_pair = 0;
-    uint32_t timing = 0;  // stages timed (bit = SM_STAGE_*), sm_set_timing
-    int dbg_flags = 0;
-    // sm_set_tuning knobs (0 = automatic)
-    int tune_ew_lanes = 0, tune_sweep_ncw = 0, tune_ew_waves = 0, tune_ew_prio = 0;
-    int tune_ew_warmup = 0, tune_sweep_lines = 0;  // in-sweep E/W lines: warmup columns, -1 off / 1 on
-    int tune_ew_guess = 0;                         // 1: the lines start from a wrong state (tests)
-    int tune_ew_start = 0;  // SM_TUNE_EW_START: 0 automatic, 1..4 the cost-derived start state, -1 the zero state
-    int tune_ew_patch = 0;  // SM_TUNE_EW_PATCH: 0 automatic, 1 the E/W patch inside the up sweep, -1 its own launch
-    int tune_bands = 0, tune_band_warmup = 0, tune_band_guess = 0;  // MODE 3 row bands (SM_TUNE_BANDS ...)
-    int tune_cost_wgs = 0;  // k_sgbm_cost2 workgroups a launch aims for (SM_TUNE_COST_WGS; 0: SGBM_COST2_WGS)
-    int tune_ply_stage = 0;  // SM_TUNE_PLY_STAGE: 0 / 1 the PLY rows staged in LDS, -1 written directly
-    int tune_sweep_xcd = 0;  // SM_TUNE_SWEEP_XCD: 1 the XCD-aware strip placement, -1 / 0 off
-    long long line_groups = 0;  // launch groups run with the in-sweep E/W lines (SM_COUNTER_LINE_GROUPS)
-    long long band_groups = 0;  // of them, with row bands (SM_COUNTER_BAND_GROUPS)
-    long long line_strips = 0;  // strips x pairs of those groups (SM_COUNTER_LINE_STRIPS)
-    std::vector<TimedEvent> pending;
-    std::vector<hipEvent_t> free_events;
-    double stage_ms[SM_NUM_STAGES] = {0};
-    long long stage_launches[SM_NUM_STAGES] = {0};
-    long long stage_pairs[SM_NUM_STAGES] = {0};
-    std::string err;
-};
-
-namespace {
-
 int fail(sm_ctx* ctx, int code, const char* fmt, ...)
 {
     char buf[512];
@@ -241,14 +122,6 @@ int fail(sm_ctx* ctx, int code, const char* fmt, ...)
     g_thread_error = buf;
     return code;
 }
-
-#define HIP_TRY(ctx, expr)                                                                           \
-    do {                                                                                              \
-        hipError_t e_ = (expr);                                                                       \
-        if (e_ != hipSuccess)                                                                         \
-            return fail((ctx), SM_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_),   \
-                        __FILE__, __LINE__);                                                          \
-    } while (0)
 
 // (re)allocate; callers make sure no queued work still uses the old buffer
 int ensure(sm_ctx* ctx, DevBuf& b, size_t bytes)
@@ -265,6 +138,48 @@ int ensure(sm_ctx* ctx, DevBuf& b, size_t bytes)
     b.n = want;
     return SM_OK;
 }
+
+hipEvent_t get_event(sm_ctx* ctx)
+{
+    if (!ctx->free_events.empty()) {
+        hipEvent_t e = ctx->free_events.back();
+        ctx->free_events.pop_back();
+        return e;
+    }
+    hipEvent_t e = nullptr;
+    (void)hipEventCreate(&e);
+    return e;
+}
+
+int stage_in(sm_ctx* ctx, std::initializer_list<StageCopy> copies)
+{
+    int rc;
+    for (const StageCopy& c : copies)
+        if ((rc = ensure(ctx, c.buf, c.bytes * std::max<size_t>(c.rows, 1))) != SM_OK) return rc;
+    StageTimer t_(ctx, ctx->stream, SM_STAGE_H2D, 1);
+    for (const StageCopy& c : copies)
+        if (c.host) HIP_TRY(ctx, hipMemcpyAsync(c.buf.p, c.host, c.bytes, hipMemcpyHostToDevice, ctx->stream));
+    return SM_OK;
+}
+
+int stage_out(sm_ctx* ctx, std::initializer_list<StageCopy> copies)
+{
+    {
+        StageTimer t_(ctx, ctx->stream, SM_STAGE_D2H, 1);
+        for (const StageCopy& c : copies) {
+            void* host = const_cast<void*>(c.host);
+            if (host && c.rows)
+                HIP_TRY(ctx, hipMemcpy2DAsync(host, c.host_pitch, c.buf.p, c.bytes, c.bytes, c.rows, hipMemcpyDeviceToHost,
+                                              ctx->stream));
+            else if (host)
+                HIP_TRY(ctx, hipMemcpyAsync(host, c.buf.p, c.bytes, hipMemcpyDeviceToHost, ctx->stream));
+        }
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return SM_OK;
+}
+
+namespace {
 
 int normalize(sm_ctx* ctx, const sm_params* p, int H, int W, Norm& n, int cn = 1)
 {
@@ -326,40 +241,6 @@ int normalize(sm_ctx* ctx, const sm_params* p, int H, int W, Norm& n, int cn = 1
     return SM_OK;
 }
 
-hipEvent_t get_event(sm_ctx* ctx)
-{
-    if (!ctx->free_events.empty()) {
-        hipEvent_t e = ctx->free_events.back();
-        ctx->free_events.pop_back();
-        return e;
-    }
-    hipEvent_t e = nullptr;
-    (void)hipEventCreate(&e);
-    return e;
-}
-
-struct StageTimer {
-    sm_ctx* ctx;
-    hipStream_t s;
-    int stage, pairs;
-    hipEvent_t a = nullptr;
-    StageTimer(sm_ctx* c, hipStream_t st, int stg, int np) : ctx(c), s(st), stage(stg), pairs(np)
-    {
-        if (ctx->timing & (1u << stage)) {
-            a = get_event(ctx);
-            (void)hipEventRecord(a, s);
-        }
-    }
-    ~StageTimer()
-    {
-        if (a) {
-            hipEvent_t b = get_event(ctx);
-            (void)hipEventRecord(b, s);
-            ctx->pending.push_back({stage, pairs, a, b});
-        }
-    }
-};
-
 void harvest_timing(sm_ctx* ctx)
 {
     for (auto& t : ctx->pending) {
@@ -374,71 +255,6 @@ void harvest_timing(sm_ctx* ctx)
     }
     ctx->pending.clear();
 }
-
-// Page-locked staging for the host-pointer entry points: inputs are packed row
-// by row into pinned memory and cross PCIe as one DMA each (a pageable
-// hipMemcpy2D moves one row per transfer: ~3 ms for a KITTI image); outputs
-// land in pinned memory and are copied out once the stream has synchronised.
-// The whole call's bytes are reserved up front, so the buffer never moves
-// while a DMA of this call is queued (host entry points are synchronous, so
-// nothing of a previous call is in flight either).
-struct HostStage {
-    struct Out {
-        void* dst;
-        size_t off, bytes;
-    };
-    sm_ctx* ctx;
-    size_t used = 0;
-    std::vector<Out> outs;
-    explicit HostStage(sm_ctx* c) : ctx(c) {}
-    int reserve(size_t bytes)
-    {
-        if (ctx->pin_n >= bytes && ctx->pin) return SM_OK;
-        if (ctx->pin) {
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            (void)hipHostFree(ctx->pin);
-            ctx->pin = nullptr;
-            ctx->pin_n = 0;
-        }
-        HIP_TRY(ctx, hipHostMalloc(&ctx->pin, bytes, hipHostMallocDefault));
-        ctx->pin_n = bytes;
-        return SM_OK;
-    }
-    uint8_t* take(size_t bytes)
-    {
-        uint8_t* p = (uint8_t*)ctx->pin + used;
-        used += (bytes + 255) & ~size_t(255);
-        return p;
-    }
-    // rows x row_bytes from host (pitch src_pitch) -> contiguous device buffer
-    int in(void* dev, const void* src, size_t rows, size_t row_bytes, size_t src_pitch)
-    {
-        uint8_t* p = take(rows * row_bytes);
-        if (src_pitch == row_bytes)
-            std::memcpy(p, src, rows * row_bytes);
-        else
-            for (size_t r = 0; r < rows; r++) std::memcpy(p + r * row_bytes, (const uint8_t*)src + r * src_pitch, row_bytes);
-        StageTimer t(ctx, ctx->stream, SM_STAGE_H2D, 1);
-        HIP_TRY(ctx, hipMemcpyAsync(dev, p, rows * row_bytes, hipMemcpyHostToDevice, ctx->stream));
-        return SM_OK;
-    }
-    int out(void* dst, const void* dev, size_t bytes)
-    {
-        uint8_t* p = take(bytes);
-        outs.push_back({dst, (size_t)(p - (uint8_t*)ctx->pin), bytes});
-        StageTimer t(ctx, ctx->stream, SM_STAGE_D2H, 1);
-        HIP_TRY(ctx, hipMemcpyAsync(p, dev, bytes, hipMemcpyDeviceToHost, ctx->stream));
-        return SM_OK;
-    }
-    int finish()
-    {
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        for (const Out& o : outs) std::memcpy(o.dst, (const uint8_t*)ctx->pin + o.off, o.bytes);
-        return SM_OK;
-    }
-};
-// staged bytes of n buffers of `bytes` each (256-byte slots)
-inline size_t stage_bytes(size_t bytes, int n = 1) { return (size_t)n * ((bytes + 255) & ~size_t(255)); }
 
 int grid_for(size_t n)
 {
@@ -732,9 +548,9 @@ bool use_hybrid(const sm_ctx* ctx, const Norm& n, int H)
     if (!SM_ABLATIONS || (n.ndirs != 8 && n.ndirs != 5) || !(ctx->dbg_flags & DBG_HYBRID) ||
         (ctx->dbg_flags & (DBG_LEGACY | DBG_SWEEP8)))
         return false;
-    sm_ctx tmp = *ctx;
-    tmp.dbg_flags = (ctx->dbg_flags & ~DBG_HYBRID) | DBG_SWEEP8;  // same preconditions as the sweeps
-    return use_sweep(&tmp, n, H);
+    // same preconditions as the sweeps: use_sweep reads neither DBG_HYBRID nor DBG_SWEEP8, so the
+    // context serves as it is (a copy would own its buffers a second time)
+    return use_sweep(ctx, n, H);
 }
 
 // preconditions of the fused sweeps (run_pairs also requires sweep_min_pairs pairs per
@@ -1467,6 +1283,8 @@ int run_hybrid(sm_ctx* ctx, const Norm& n, const Geo& g, BufSet& bs)
     return SM_OK;
 }
 
+}  // namespace
+
 // sticky device-side error of the unguarded (hybrid) sweep use; clears it.  The
 // default sweep engine recovers on the device instead (run_group's fallback).
 int check_sweep_errors(sm_ctx* ctx)
@@ -1485,6 +1303,8 @@ int check_sweep_errors(sm_ctx* ctx)
     }
     return SM_OK;
 }
+
+namespace {
 
 // Cost volumes leave with nontemporal stores when the launch group's volume cannot stay in
 // the 256 MB Infinity Cache anyway (census8, 8 KITTI pairs: 227.3 -> 219.9 us per pair, the
@@ -2533,27 +2353,7 @@ void sm_destroy(sm_ctx* ctx)
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     (void)hipDeviceSynchronize();
-    DevBuf* bufs[] = {&ctx->img[0],  &ctx->img[1],  &ctx->planes,    &ctx->out,         &ctx->dbg,
-                      &ctx->volbuf,  &ctx->wls_num, &ctx->wls_den,   &ctx->wls_inter,   &ctx->wls_disp[0], &ctx->wls_w,
-                      &ctx->wls_disp[1], &ctx->wls_out, &ctx->sp_parent, &ctx->sp_count,
-                      &ctx->rp_in,   &ctx->rp_out,  &ctx->rp_min,    &ctx->bm_pre[0],   &ctx->bm_pre[1],
-                      &ctx->bm_cost, &ctx->hop,     &ctx->sweep_err, &ctx->wls_R,      &ctx->wls_IT,
-                      &ctx->volwin,  &ctx->rm_src,  &ctx->rm_mapx,   &ctx->rm_mapy,     &ctx->rm_dst,
-                      &ctx->rm_gray, &ctx->nlm_tab, &ctx->cl_tot,    &ctx->cl_off,      &ctx->ply_tot,
-                      &ctx->ply_off, &ctx->cl_verts, &ctx->cl_colors, &ctx->cl_out,      &ctx->flt_a,
-                      &ctx->png_stream, &ctx->png_slots, &ctx->png_seg, &ctx->png_off, &ctx->png_img,
-                      &ctx->png_range, &ctx->png_in, &ctx->png_out, &ctx->png_nb,
-                      &ctx->pd_img, &ctx->pd_chunks, &ctx->pd_idat, &ctx->pd_cinfo, &ctx->pd_slots, &ctx->pd_zbuf,
-                      &ctx->pd_stream, &ctx->pd_seg, &ctx->pd_carry, &ctx->pd_in, &ctx->pd_tab, &ctx->pd_out,
-                      &ctx->pd_status, &ctx->jd_img, &ctx->jd_iv, &ctx->jd_state, &ctx->jd_lane, &ctx->jd_coef,
-                      &ctx->jd_planes, &ctx->jd_in, &ctx->jd_desc, &ctx->jd_tab, &ctx->jd_out, &ctx->jd_status};
-    for (DevBuf* b : bufs)
-        if (b->p) (void)hipFree(b->p);
     for (auto& bs : ctx->set) {
-        DevBuf* sb[] = {&bs.census[0], &bs.census[1], &bs.cost, &bs.L,  &bs.raw,
-                        &bs.part,      &bs.key2,      &bs.pre,  &bs.st, &bs.vst};
-        for (DevBuf* b : sb)
-            if (b->p) (void)hipFree(b->p);
         if (bs.paths_done) (void)hipEventDestroy(bs.paths_done);
         if (bs.wta_done) (void)hipEventDestroy(bs.wta_done);
     }
@@ -2992,1551 +2792,6 @@ int sm_filter_speckles(sm_ctx* ctx, int16_t* img, int H, int W, int new_val, int
     }
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return check_sweep_errors(ctx);
-}
-
-int sm_reproject_image_to_3d_device(sm_ctx* ctx, const void* d_disp, int disp_type, int nimg, int H, int W,
-                                    const double* Q, int handle_missing, float* d_xyz)
-{
-    if (!ctx) return fail(nullptr, SM_E_ARG, "ctx is NULL");
-    if (!d_disp || !d_xyz || !Q || nimg < 0 || H <= 0 || W <= 0) return fail(ctx, SM_E_ARG, "bad arguments");
-    if (disp_type != SM_DISP_S16 && disp_type != SM_DISP_F32)
-        return fail(ctx, SM_E_UNSUPPORTED, "disparity type %d not supported (int16 or float32)", disp_type);
-    if (nimg == 0) return SM_OK;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    smk::ReprojArgs ra{};
-    ra.disp = d_disp;
-    ra.xyz = d_xyz;
-    std::memcpy(ra.Q, Q, sizeof ra.Q);
-    ra.H = H;
-    ra.W = W;
-    ra.handle_missing = handle_missing != 0;
-    const size_t npx = (size_t)H * W;
-    if (ra.handle_missing) {
-        int rc;
-        if ((rc = ensure(ctx, ctx->rp_min, (size_t)nimg * 8)) != SM_OK) return rc;
-        int* keys = (int*)ctx->rp_min.p;
-        HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)keys, 0x7FFFFFFF, nimg, ctx->stream));
-        const dim3 g((unsigned)std::min<size_t>((npx + 255) / 256, 1024), nimg);
-        if (disp_type == SM_DISP_S16)
-            hipLaunchKernelGGL(smk::k_disp_min<int16_t>, g, dim3(256), 0, ctx->stream, (const int16_t*)d_disp, keys, npx);
-        else
-            hipLaunchKernelGGL(smk::k_disp_min<float>, g, dim3(256), 0, ctx->stream, (const float*)d_disp, keys, npx);
-        hipLaunchKernelGGL(smk::k_keys_to_float, dim3((nimg + 63) / 64), dim3(64), 0, ctx->stream, keys,
-                           (float*)(keys + nimg), nimg);
-        ra.min_disp = (const float*)(keys + nimg);
-    }
-    const dim3 grid((W + 255) / 256, H, nimg);
-    if (disp_type == SM_DISP_S16)
-        hipLaunchKernelGGL(smk::k_reproject<int16_t>, grid, dim3(256), 0, ctx->stream, ra);
-    else
-        hipLaunchKernelGGL(smk::k_reproject<float>, grid, dim3(256), 0, ctx->stream, ra);
-    HIP_TRY(ctx, hipGetLastError());
-    return SM_OK;
-}
-
-int sm_reproject_image_to_3d(sm_ctx* ctx, const void* disp, int disp_type, int H, int W, const double* Q,
-                             int handle_missing, float* xyz)
-{
-    if (!ctx) return fail(nullptr, SM_E_ARG, "ctx is NULL");
-    if (!disp || !xyz || !Q || H <= 0 || W <= 0) return fail(ctx, SM_E_ARG, "bad arguments");
-    if (disp_type != SM_DISP_S16 && disp_type != SM_DISP_F32)
-        return fail(ctx, SM_E_UNSUPPORTED, "disparity type %d not supported (int16 or float32)", disp_type);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t npx = (size_t)H * W, ib = npx * (disp_type == SM_DISP_S16 ? 2 : 4);
-    int rc;
-    if ((rc = ensure(ctx, ctx->rp_in, ib)) != SM_OK) return rc;
-    if ((rc = ensure(ctx, ctx->rp_out, npx * 12)) != SM_OK) return rc;
-    {
-        StageTimer t_(ctx, ctx->stream, SM_STAGE_H2D, 1);
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->rp_in.p, disp, ib, hipMemcpyHostToDevice, ctx->stream));
-    }
-    if ((rc = sm_reproject_image_to_3d_device(ctx, ctx->rp_in.p, disp_type, 1, H, W, Q, handle_missing,
-                                              (float*)ctx->rp_out.p)) != SM_OK)
-        return rc;
-    {
-        StageTimer t_(ctx, ctx->stream, SM_STAGE_D2H, 1);
-        HIP_TRY(ctx, hipMemcpyAsync(xyz, ctx->rp_out.p, npx * 12, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return check_sweep_errors(ctx);
-}
-
-// ---- rectification front end (sm_rectify.hpp)
-namespace {
-constexpr int kRectMaxDim = 16384;
-
-bool aligned_to(const void* p, size_t n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1)) == 0; }
-}  // namespace
-
-int sm_rectify_map_device(sm_ctx* ctx, const sm_rectify_cam* cam, int H, int W, float* d_mapx, float* d_mapy)
-{
-    if (!ctx) return fail(nullptr, SM_E_ARG, "ctx is NULL");
-    if (!cam || !d_mapx || !d_mapy) return fail(ctx, SM_E_ARG, "rectify map: NULL argument");
-    if (H <= 0 || W <= 0 || H > kRectMaxDim || W > kRectMaxDim)
-        return fail(ctx, SM_E_ARG, "rectify map: size %d x %d outside 1..%d", W, H, kRectMaxDim);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    smk::RectMapArgs a{};
-    std::memcpy(a.iR, cam->iR, sizeof a.iR);
-    a.k1 = cam->dist[0], a.k2 = cam->dist[1], a.p1 = cam->dist[2], a.p2 = cam->dist[3], a.k3 = cam->dist[4];
-    a.fx = cam->K[0], a.fy = cam->K[4], a.cx = cam->K[2], a.cy = cam->K[5];
-    a.mapx = d_mapx, a.mapy = d_mapy, a.H = H, a.W = W;
-    hipLaunchKernelGGL(smk::k_rectify_map, dim3((W + 255) / 256, H), dim3(256), 0, ctx->stream, a);
-    HIP_TRY(ctx, hipGetLastError());
-    return SM_OK;
-}
-
-int sm_rectify_map(sm_ctx* ctx, const sm_rectify_cam* cam, int H, int W, float* mapx, float* mapy)
-{
-    if (!ctx) return fail(nullptr, SM_E_ARG, "ctx is NULL");
-    if (!cam || !mapx || !mapy) return fail(ctx, SM_E_ARG, "rectify map: NULL argument");
-    if (H <= 0 || W <= 0 || H > kRectMaxDim || W > kRectMaxDim)
-        return fail(ctx, SM_E_ARG, "rectify map: size %d x %d outside 1..%d", W, H, kRectMaxDim);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t mb = (size_t)H * W * 4;
-    int rc;
-    if ((rc = ensure(ctx, ctx->rm_mapx, mb)) != SM_OK) return rc;
-    if ((rc = ensure(ctx, ctx->rm_mapy, mb)) != SM_OK) return rc;
-    if ((rc = sm_rectify_map_device(ctx, cam, H, W, (float*)ctx->rm_mapx.p, (float*)ctx->rm_mapy.p)) != SM_OK) return rc;
-    {
-        StageTimer t_(ctx, ctx->stream, SM_STAGE_D2H, 1);
-        HIP_TRY(ctx, hipMemcpyAsync(mapx, ctx->rm_mapx.p, mb, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(mapy, ctx->rm_mapy.p, mb, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return SM_OK;
-}
-
-namespace {
-int remap_check(sm_ctx* ctx, const void* src, int srcH, int srcW, int src_stride, int channels, const void* mapx,
-                const void* mapy, int H, int W, const void* dst, const void* gray)
-{
-    if (!src || !mapx || !mapy) return fail(ctx, SM_E_ARG, "remap: NULL source or map");
-    if (!dst && !gray) return fail(ctx, SM_E_ARG, "remap: both outputs are NULL");
-    if (channels != 1 && channels != 3) return fail(ctx, SM_E_ARG, "remap: channels %d (1 or 3)", channels);
-    if (gray && channels != 3) return fail(ctx, SM_E_ARG, "remap: the gray output needs a 3-channel (BGR) source");
-    if (srcH <= 0 || srcW <= 0 || srcH > kRectMaxDim || srcW > kRectMaxDim)
-        return fail(ctx, SM_E_ARG, "remap: source size %d x %d outside 1..%d", srcW, srcH, kRectMaxDim);
-    if (H <= 0 || W <= 0 || H > kRectMaxDim || W > kRectMaxDim)
-        return fail(ctx, SM_E_ARG, "remap: destination size %d x %d outside 1..%d", W, H, kRectMaxDim);
-    if (src_stride < srcW * channels) return fail(ctx, SM_E_ARG, "remap: src_stride %d < %d", src_stride, srcW * channels);
-    return SM_OK;
-}
-}  // namespace
-
-int sm_remap_u8_batch_device(sm_ctx* ctx, const uint8_t* d_src, int nimg, size_t img_stride_bytes, int srcH, int srcW,
-                             int src_stride, int channels, const float* d_mapx, const float* d_mapy, int H, int W,
-                             uint8_t* d_dst, uint8_t* d_gray)
-{
-    if (!ctx) return fail(nullptr, SM_E_ARG, "ctx is NULL");
-    int rc;
-    if ((rc = remap_check(ctx, d_src, srcH, srcW, src_stride, channels, d_mapx, d_mapy, H, W, d_dst, d_gray)) != SM_OK)
-        return rc;
-    if (nimg < 0 || nimg > 65535 * smk::REMAP_IPT) return fail(ctx, SM_E_ARG, "remap: nimg %d", nimg);
-    if (nimg > 1 && img_stride_bytes < (size_t)(srcH - 1) * src_stride + (size_t)srcW * channels)
-        return fail(ctx, SM_E_ARG, "remap: img_stride_bytes %zu smaller than one image", img_stride_bytes);
-    if (nimg == 0) return SM_OK;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    smk::RemapArgs a{};
-    a.src = d_src, a.mapx = d_mapx, a.mapy = d_mapy, a.dst = d_dst, a.gray = d_gray;
-    a.img_stride = img_stride_bytes;
-    a.nimg = nimg, a.srcH = srcH, a.srcW = srcW, a.src_stride = src_stride, a.H = H, a.W = W;
-    a.Wq = (W + 3) / 4;
-    a.vec = W % 4 == 0 && aligned_to(d_mapx, 16) && aligned_to(d_mapy, 16) && aligned_to(d_dst, 4) &&
-            aligned_to(d_gray, 4);
-    const dim3 grid(((unsigned)H * a.Wq + 255) / 256, (nimg + smk::REMAP_IPT - 1) / smk::REMAP_IPT);
-    if (channels == 1)
-        hipLaunchKernelGGL((smk::k_remap_u8<1, false>), grid, dim3(256), 0, ctx->stream, a);
-    else if (d_gray)
-        hipLaunchKernelGGL((smk::k_remap_u8<3, true>), grid, dim3(256), 0, ctx->stream, a);
-    else
-        hipLaunchKernelGGL((smk::k_remap_u8<3, false>), grid, dim3(256), 0, ctx->stream, a);
-    HIP_TRY(ctx, hipGetLastError());
-    return SM_OK;
-}
-
-int sm_remap_u8(sm_ctx* ctx, const uint8_t* src, int srcH, int srcW, int src_stride, int channels, const float* mapx,
-                const float* mapy, int H, int W, uint8_t* dst, uint8_t* gray)
-{
-    if (!ctx) return fail(nullptr, SM_E_ARG, "ctx is NULL");
-    int rc;
-    if ((rc = remap_check(ctx, src, srcH, srcW, src_stride, channels, mapx, mapy, H, W, dst, gray)) != SM_OK) return rc;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t sb = (size_t)(srcH - 1) * src_stride + (size_t)srcW * channels, npx = (size_t)H * W;
-    if ((rc = ensure(ctx, ctx->rm_src, sb)) != SM_OK) return rc;
-    if ((rc = ensure(ctx, ctx->rm_mapx, npx * 4)) != SM_OK) return rc;
-    if ((rc = ensure(ctx, ctx->rm_mapy, npx * 4)) != SM_OK) return rc;
-    if (dst && (rc = ensure(ctx, ctx->rm_dst, npx * channels)) != SM_OK) return rc;
-    if (gray && (rc = ensure(ctx, ctx->rm_gray, npx)) != SM_OK) return rc;
-    {
-        StageTimer t_(ctx, ctx->stream, SM_STAGE_H2D, 1);
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->rm_src.p, src, sb, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->rm_mapx.p, mapx, npx * 4, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->rm_mapy.p, mapy, npx * 4, hipMemcpyHostToDevice, ctx->stream));
-    }
-    if ((rc = sm_remap_u8_batch_device(ctx, (const uint8_t*)ctx->rm_src.p, 1, 0, srcH, srcW, src_stride, channels,
-                                       (const float*)ctx->rm_mapx.p, (const float*)ctx->rm_mapy.p, H, W,
-                                       dst ? (uint8_t*)ctx->rm_dst.p : nullptr,
-                                       gray ? (uint8_t*)ctx->rm_gray.p : nullptr)) != SM_OK)
-        return rc;
-    {
-        StageTimer t_(ctx, ctx->stream, SM_STAGE_D2H, 1);
-        if (dst) HIP_TRY(ctx, hipMemcpyAsync(dst, ctx->rm_dst.p, npx * channels, hipMemcpyDeviceToHost, ctx->stream));
-        if (gray) HIP_TRY(ctx, hipMemcpyAsync(gray, ctx->rm_gray.p, npx, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return SM_OK;
-}
-
-int sm_bgr2gray_u8_batch_device(sm_ctx* ctx, const uint8_t* d_src, int nimg, size_t img_stride_bytes, int H, int W,
-                                int src_stride, uint8_t* d_gray)
-{
-    if (!ctx) return fail(nullptr, SM_E_ARG, "ctx is NULL");
-    if (!d_src || !d_gray) return fail(ctx, SM_E_ARG, "bgr2gray: NULL argument");
-    if (H <= 0 || W <= 0 || H > kRectMaxDim || W > kRectMaxDim)
-        return fail(ctx, SM_E_ARG, "bgr2gray: size %d x %d outside 1..%d", W, H, kRectMaxDim);
-    if (src_stride < W * 3) return fail(ctx, SM_E_ARG, "bgr2gray: src_stride %d < %d", src_stride, W * 3);
-    if (nimg < 0 || nimg > 65535) return fail(ctx, SM_E_ARG, "bgr2gray: nimg %d", nimg);
-    if (nimg > 1 && img_stride_bytes < (size_t)(H - 1) * src_stride + (size_t)W * 3)
-        return fail(ctx, SM_E_ARG, "bgr2gray: img_stride_bytes %zu smaller than one image", img_stride_bytes);
-    if (nimg == 0) return SM_OK;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    smk::GrayArgs a{};
-    a.src = d_src, a.gray = d_gray, a.img_stride = img_stride_bytes, a.H = H, a.W = W, a.src_stride = src_stride;
-    hipLaunchKernelGGL(smk::k_bgr2gray, dim3((W + 255) / 256, H, nimg), dim3(256), 0, ctx->stream, a);
-    HIP_TRY(ctx, hipGetLastError());
-    return SM_OK;
-}
-
-int sm_bgr2gray_u8(sm_ctx* ctx, const uint8_t* src, int H, int W, int src_stride, uint8_t* gray)
-{
-    if (!ctx) return fail(nullptr, SM_E_ARG, "ctx is NULL");
-    if (!src || !gray) return fail(ctx, SM_E_ARG, "bgr2gray: NULL argument");
-    if (H <= 0 || W <= 0 || H > kRectMaxDim || W > kRectMaxDim)
-        return fail(ctx, SM_E_ARG, "bgr2gray: size %d x %d outside 1..%d", W, H, kRectMaxDim);
-    if (src_stride < W * 3) return fail(ctx, SM_E_ARG, "bgr2gray: src_stride %d < %d", src_stride, W * 3);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t sb = (size_t)(H - 1) * src_stride + (size_t)W * 3, npx = (size_t)H * W;
-    int rc;
-    if ((rc = ensure(ctx, ctx->rm_src, sb)) != SM_OK) return rc;
-    if ((rc = ensure(ctx, ctx->rm_gray, npx)) != SM_OK) return rc;
-    {
-        StageTimer t_(ctx, ctx->stream, SM_STAGE_H2D, 1);
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->rm_src.p, src, sb, hipMemcpyHostToDevice, ctx->stream));
-    }
-    if ((rc = sm_bgr2gray_u8_batch_device(ctx, (const uint8_t*)ctx->rm_src.p, 1, 0, H, W, src_stride,
-                                          (uint8_t*)ctx->rm_gray.p)) != SM_OK)
-        return rc;
-    {
-        StageTimer t_(ctx, ctx->stream, SM_STAGE_D2H, 1);
-        HIP_TRY(ctx, hipMemcpyAsync(gray, ctx->rm_gray.p, npx, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return SM_OK;
-}
-
-// ---- fastNlMeansDenoising (sm_nlm.hpp)
-namespace {
-struct NlmGeo {
-    int th, sh, t, s, fpm, shift, n;
-    double mult;
-};
-
-// window sizes and h checked, and the table's constants (the only floating-point part)
-int nlm_geo(sm_ctx* ctx, float h, int template_window, int search_window, NlmGeo& g)
-{
-    if (template_window < 1) return fail(ctx, SM_E_ARG, "nlm: templateWindowSize %d < 1", template_window);
-    if (search_window < 1) return fail(ctx, SM_E_ARG, "nlm: searchWindowSize %d < 1", search_window);
-    if (!(h >= 0.f) || std::isinf(h)) return fail(ctx, SM_E_ARG, "nlm: h = %g (a finite h >= 0 is needed)", (double)h);
-    g.th = template_window / 2, g.sh = search_window / 2;
-    g.t = 2 * g.th + 1, g.s = 2 * g.sh + 1;
-    if (g.th > smk::NLM_MAX_TH)
-        return fail(ctx, SM_E_UNSUPPORTED, "nlm: templateWindowSize %d (template %d x %d) not built: 1..%d",
-                    template_window, g.t, g.t, 2 * smk::NLM_MAX_TH + 1);
-    if (g.sh > smk::NLM_MAX_SH)
-        return fail(ctx, SM_E_UNSUPPORTED, "nlm: searchWindowSize %d (search %d x %d) not built: 1..%d", search_window,
-                    g.s, g.s, 2 * smk::NLM_MAX_SH + 1);
-    g.fpm = INT32_MAX / (g.s * g.s * 255);
-    g.shift = 0;
-    while ((1 << g.shift) < g.t * g.t) g.shift++;
-    g.mult = double(1 << g.shift) / double(g.t * g.t);
-    g.n = int(65025.0 / g.mult + 1);
-    return SM_OK;
-}
-
-// tab[a] = rint(fpm * exp(-(a * mult) / (h * h))) (h * h in float32; a NaN weight, h = 0 at
-// a = 0, counts as 1), entries below fpm / 1000 zeroed; returns the non-zero prefix's length
-int nlm_table(const NlmGeo& g, float h, int32_t* tab)
-{
-    const float hhf = h * h;
-    const double hh = (double)hhf, floor_w = 0.001 * g.fpm;
-    int last = 0;
-    for (int a = 0; a < g.n; a++) {
-        double w = std::exp(-(a * g.mult) / hh);
-        if (w != w) w = 1.0;
-        int v = (int)std::nearbyint(g.fpm * w);  // the default rounding mode: half to even
-        if (v < floor_w) v = 0;
-        tab[a] = v;
-        if (v) last = a + 1;
-    }
-    return last;
-}
-
-// the device copy of the table's non-zero prefix for (h, t, s), cached in the context
-int ensure_nlm_table(sm_ctx* ctx, const NlmGeo& g, float h)
-{
-    uint32_t hb;
-    std::memcpy(&hb, &h, 4);
-    if (ctx->nlm_ntab > 0 && ctx->nlm_key_h == hb && ctx->nlm_key_t == g.t && ctx->nlm_key_s == g.s) return SM_OK;
-    // launches that read the old table (on whichever stream they were queued) finish first
-    HIP_TRY(ctx, hipDeviceSynchronize());
-    ctx->nlm_ntab = 0;
-    ctx->nlm_tab_host.resize(g.n);
-    const int ntab = nlm_table(g, h, ctx->nlm_tab_host.data());
-    int rc;
-    if ((rc = ensure(ctx, ctx->nlm_tab, (size_t)ntab * 4)) != SM_OK) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->nlm_tab.p, ctx->nlm_tab_host.data(), (size_t)ntab * 4, hipMemcpyHostToDevice,
-                                ctx->stream));
-    // once per (h, t, s): the table is complete before a launch on any other stream uses it,
-    // and nlm_tab_host (kept anyway) is not touched while the copy runs
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->nlm_key_h = hb, ctx->nlm_key_t = g.t, ctx->nlm_key_s = g.s, ctx->nlm_shift = g.shift;
-    ctx->nlm_ntab = ntab;
-    return SM_OK;
-}
-
-int nlm_image_check(sm_ctx* ctx, const void* src, const void* dst, int H, int W, int src_stride)
-{
-    if (H <= 0 || W <= 0 || H > kRectMaxDim || W > kRectMaxDim)
-        return fail(ctx, SM_E_ARG, "nlm: size %d x %d outside 1..%d", W, H, kRectMaxDim);
-    if (!src || !dst) return fail(ctx, SM_E_ARG, "nlm: NULL argument");
-    if (src_stride < W) return fail(ctx, SM_E_ARG, "nlm: src_stride %d < %d", src_stride, W);
-    return SM_OK;
-}
-}  // namespace
-
-int sm_nlm_weight_table(float h, int template_window, int search_window, int32_t* tab, int* n, int* fpm, int* shift)
-{
-    NlmGeo g;
-    int rc;
-    if ((rc = nlm_geo(nullptr, h, template_window, search_window, g)) != SM_OK) return rc;
-    if (n) *n = g.n;
-    if (fpm) *fpm = g.fpm;
-    if (shift) *shift = g.shift;
-    if (tab) nlm_table(g, h, tab);
-    return SM_OK;
-}
-
-int sm_nlm_denoise_u8_batch_device(sm_ctx* ctx, const uint8_t* d_src, int nimg, size_t img_stride_bytes, int H, int W,
-                                   int src_stride, float h, int template_window, int search_window, uint8_t* d_dst)
-{
-    if (!ctx) return fail(nullptr, SM_E_ARG, "ctx is NULL");
-    int rc;
-    NlmGeo g;
-    if ((rc = nlm_image_check(ctx, d_src, d_dst, H, W, src_stride)) != SM_OK) return rc;
-    if ((rc = nlm_geo(ctx, h, template_window, search_window, g)) != SM_OK) return rc;
-    if (nimg < 0 || nimg > 65535) return fail(ctx, SM_E_ARG, "nlm: nimg %d", nimg);
-    if (nimg > 1 && img_stride_bytes < (size_t)(H - 1) * src_stride + (size_t)W)
-        return fail(ctx, SM_E_ARG, "nlm: img_stride_bytes %zu smaller than one image", img_stride_bytes);
-    if (nimg == 0) return SM_OK;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if ((rc = ensure_nlm_table(ctx, g, h)) != SM_OK) return rc;
-    smk::NlmArgs a{};
-    a.src = d_src, a.dst = d_dst, a.tab = (const int32_t*)ctx->nlm_tab.p;
-    a.img_stride = img_stride_bytes;
-    a.H = H, a.W = W, a.src_stride = src_stride;
-    a.sh = g.sh, a.shift = ctx->nlm_shift, a.ntab = ctx->nlm_ntab;
-    a.pitch = smk::nlm_pitch(g.th, g.sh);
-    const bool lds_tab = a.ntab <= smk::NLM_LDS_TAB_MAX;
-    const size_t lds = smk::nlm_lds_bytes(g.th, g.sh, lds_tab ? a.ntab : 0);
-    const dim3 grid((W + smk::NLM_TILE - 1) / smk::NLM_TILE, (H + smk::NLM_TILE - 1) / smk::NLM_TILE, nimg);
-    if (lds_tab)
-        smk::nlm_launch<true>(g.th, grid, lds, ctx->stream, a);
-    else
-        smk::nlm_launch<false>(g.th, grid, lds, ctx->stream, a);
-    HIP_TRY(ctx, hipGetLastError());
-    return SM_OK;
-}
-
-int sm_nlm_denoise_u8(sm_ctx* ctx, const uint8_t* src, int H, int W, int src_stride, float h, int template_window,
-                      int search_window, uint8_t* dst)
-{
-    if (!ctx) return fail(nullptr, SM_E_ARG, "ctx is NULL");
-    int rc;
-    NlmGeo g;
-    if ((rc = nlm_image_check(ctx, src, dst, H, W, src_stride)) != SM_OK) return rc;
-    if ((rc = nlm_geo(ctx, h, template_window, search_window, g)) != SM_OK) return rc;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t sb = (size_t)(H - 1) * src_stride + (size_t)W, npx = (size_t)H * W;
-    if ((rc = ensure(ctx, ctx->rm_src, sb)) != SM_OK) return rc;
-    if ((rc = ensure(ctx, ctx->rm_gray, npx)) != SM_OK) return rc;
-    {
-        StageTimer t_(ctx, ctx->stream, SM_STAGE_H2D, 1);
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->rm_src.p, src, sb, hipMemcpyHostToDevice, ctx->stream));
-    }
-    if ((rc = sm_nlm_denoise_u8_batch_device(ctx, (const uint8_t*)ctx->rm_src.p, 1, 0, H, W, src_stride, h,
-                                             template_window, search_window, (uint8_t*)ctx->rm_gray.p)) != SM_OK)
-        return rc;
-    {
-        StageTimer t_(ctx, ctx->stream, SM_STAGE_D2H, 1);
-        HIP_TRY(ctx, hipMemcpyAsync(dst, ctx->rm_gray.p, npx, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return SM_OK;
-}
-
-// ---- gaussian_filter, image_measure and pyrDown (sm_filter.hpp)
-namespace {
-
-// the half kernel of one axis into the kernel arguments; NULL or r = 0: the identity
-int gauss_axis(sm_ctx* ctx, const char* who, const char* axis, const double* w, int r, double* out, int& r_out)
-{
-    if (r < 0) return fail(ctx, SM_E_ARG, "%s: radius %d of axis %s < 0", who, r, axis);
-    if (r > smk::GF_MAX_R)
-        return fail(ctx, SM_E_UNSUPPORTED, "%s: radius %d of axis %s not built: 0..%d", who, r, axis, smk::GF_MAX_R);
-    if (!w || r == 0) {
-        out[0] = 1.0;
-        r_out = 0;
-        return SM_OK;
-    }
-    std::copy(w, w + r + 1, out);
-    r_out = r;
-    return SM_OK;
-}
-
-int filter_image_check(sm_ctx* ctx, const char* who, const void* src, const void* dst, int nimg, int H, int W)
-{
-    if (H <= 0 || W <= 0 || H > kRectMaxDim || W > kRectMaxDim)
-        return fail(ctx, SM_E_ARG, "%s: size %d x %d outside 1..%d", who, W, H, kRectMaxDim);
-    if (!src || !dst) return fail(ctx, SM_E_ARG, "%s: NULL argument", who);
-    if (nimg < 0 || nimg > 65535) return fail(ctx, SM_E_ARG, "%s: nimg %d", who, nimg);
-    return SM_OK;
-}
-
-// elements from the first image's first to the last image's last
-size_t filter_span(int nimg, size_t img_stride, int H, int W, int stride)
-{
-    return (size_t)(nimg - 1) * img_stride + (size_t)(H - 1) * stride + (size_t)W;
-}
-
-extern "C++" template <bool BGR, bool UNSHARP>
-int gauss_launch(sm_ctx* ctx, const smk::GaussArgs& a, int nimg)
-{
-    const size_t lds = smk::gauss_lds_bytes(a.ry, a.rx);
-    const auto kernel = smk::k_gauss2d_f64<BGR, UNSHARP>;
-    if (lds > 48 * 1024)  // above the default limit of dynamic LDS
-        HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const dim3 grid((a.W + smk::GF_TW - 1) / smk::GF_TW, (a.H + smk::GF_TH - 1) / smk::GF_TH, nimg);
-    hipLaunchKernelGGL(kernel, grid, dim3(smk::GF_THREADS), lds, ctx->stream, a);
-    HIP_TRY(ctx, hipGetLastError());
-    return SM_OK;
-}
-
-}  // namespace
-
-int sm_gauss2d_f64_batch_device(sm_ctx* ctx, const double* d_src, int nimg, size_t src_img_stride, int H, int W,
-                                int src_stride, const double* wy, int ry, const double* wx, int rx, double* d_dst,
-                                size_t dst_img_stride, int dst_stride)
-{
-    if (!ctx) return fail(nullptr, SM_E_ARG, "ctx is NULL");
-    int rc;
-    if ((rc = filter_image_check(ctx, "gauss2d", d_src, d_dst, nimg, H, W)) != SM_OK) return rc;
-    if (src_stride < W || dst_stride < W)
-        return fail(ctx, SM_E_ARG, "gauss2d: row stride %d / %d < %d", src_stride, dst_stride, W);
-    if (nimg > 1 && (src_img_stride < filter_span(1, 0, H, W, src_stride) ||
-                     dst_img_stride < filter_span(1, 0, H, W, dst_stride)))
-        return fail(ctx, SM_E_ARG, "gauss2d: image stride %zu / %zu smaller than one image", src_img_stride,
-                    dst_img_stride);
-    smk::GaussArgs a{};
-    if ((rc = gauss_axis(ctx, "gauss2d", "0", wy, ry, a.wy, a.ry)) != SM_OK) return rc;
-    if ((rc = gauss_axis(ctx, "gauss2d", "1", wx, rx, a.wx, a.rx)) != SM_OK) return rc;
-    if (nimg == 0) return SM_OK;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    a.src = d_src, a.dst = d_dst, a.src_img_stride = src_img_stride, a.dst_img_stride = dst_img_stride;
-    a.H = H, a.W = W, a.src_stride = src_stride, a.dst_stride = dst_stride;
-    return gauss_launch<false, false>(ctx, a, nimg);
-}
-
-int sm_gauss2d_f64(sm_ctx* ctx, const double* src, int nimg, size_t src_img_stride, int H, int W, int src_stride,
-                   const double* wy, int ry, const double* wx, int rx, double* dst)
-{
-    if (!ctx) return fail(nullptr, SM_E_ARG, "ctx is NULL");
-    int rc;
-    if ((rc = filter_image_check(ctx, "gauss2d", src, dst, nimg, H, W)) != SM_OK) return rc;
-    if (src_stride < W) return fail(ctx, SM_E_ARG, "gauss2d: row stride %d < %d", src_stride, W);
-    if (nimg == 0) return SM_OK;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t sb = filter_span(nimg, src_img_stride, H, W, src_stride) * 8, db = (size_t)nimg * H * W * 8;
-    if ((rc = ensure(ctx, ctx->rm_src, sb)) != SM_OK) return rc;
-    if ((rc = ensure(ctx, ctx->rm_dst, db)) != SM_OK) return rc;
-    {
-        StageTimer t_(ctx, ctx->stream, SM_STAGE_H2D, 1);
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->rm_src.p, src, sb, hipMemcpyHostToDevice, ctx->stream));
-    }
-    if ((rc = sm_gauss2d_f64_batch_device(ctx, (const double*)ctx->rm_src.p, nimg, src_img_stride, H, W, src_stride,
-                                          wy, ry, wx, rx, (double*)ctx->rm_dst.p, (size_t)H * W, W)) != SM_OK)
-        return rc;
-    {
-        StageTimer t_(ctx, ctx->stream, SM_STAGE_D2H, 1);
-        HIP_TRY(ctx, hipMemcpyAsync(dst, ctx->rm_dst.p, db, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return SM_OK;
-}
-
-int sm_image_measure_u8_batch_device(sm_ctx* ctx, const uint8_t* d_bgr, int nimg, size_t img_stride_bytes, int H, int W,
-                                     int src_stride, const double* w1, int r1, const double* w2, int r2, double alpha,
-                                     double* d_dst)
-{
-    if (!ctx) return fail(nullptr, SM_E_ARG, "ctx is NULL");
-    int rc;
-    if ((rc = filter_image_check(ctx, "image_measure", d_bgr, d_dst, nimg, H, W)) != SM_OK) return rc;
-    if (src_stride < W * 3) return fail(ctx, SM_E_ARG, "image_measure: src_stride %d < %d", src_stride, W * 3);
-    if (nimg > 1 && img_stride_bytes < (size_t)(H - 1) * src_stride + (size_t)W * 3)
-        return fail(ctx, SM_E_ARG, "image_measure: img_stride_bytes %zu smaller than one image", img_stride_bytes);
-    smk::GaussArgs a{}, b{};
-    if ((rc = gauss_axis(ctx, "image_measure", "0 and 1 of the first filter", w1, r1, a.wy, a.ry)) != SM_OK) return rc;
-    if ((rc = gauss_axis(ctx, "image_measure", "0 and 1 of the second filter", w2, r2, b.wy, b.ry)) != SM_OK) return rc;
-    std::copy(a.wy, a.wy + a.ry + 1, a.wx), a.rx = a.ry;
-    std::copy(b.wy, b.wy + b.ry + 1, b.wx), b.rx = b.ry;
-    if (nimg == 0) return SM_OK;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t npx = (size_t)H * W;
-    // a reallocation waits for the whole device (ensure), so no earlier launch still uses flt_a
-    if ((rc = ensure(ctx, ctx->flt_a, (size_t)nimg * npx * 8)) != SM_OK) return rc;
-    a.src = d_bgr, a.dst = (double*)ctx->flt_a.p, a.src_img_stride = img_stride_bytes, a.dst_img_stride = npx;
-    a.H = H, a.W = W, a.src_stride = src_stride, a.dst_stride = W;
-    if ((rc = gauss_launch<true, false>(ctx, a, nimg)) != SM_OK) return rc;
-    b.src = ctx->flt_a.p, b.dst = d_dst, b.src_img_stride = npx, b.dst_img_stride = npx;
-    b.H = H, b.W = W, b.src_stride = W, b.dst_stride = W, b.alpha = alpha;
-    return gauss_launch<false, true>(ctx, b, nimg);
-}
-
-int sm_image_measure_u8(sm_ctx* ctx, const uint8_t* bgr, int H, int W, int src_stride, const double* w1, int r1,
-                        const double* w2, int r2, double alpha, double* dst)
-{
-    if (!ctx) return fail(nullptr, SM_E_ARG, "ctx is NULL");
-    int rc;
-    if ((rc = filter_image_check(ctx, "image_measure", bgr, dst, 1, H, W)) != SM_OK) return rc;
-    if (src_stride < W * 3) return fail(ctx, SM_E_ARG, "image_measure: src_stride %d < %d", src_stride, W * 3);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t sb = (size_t)(H - 1) * src_stride + (size_t)W * 3, db = (size_t)H * W * 8;
-    if ((rc = ensure(ctx, ctx->rm_src, sb)) != SM_OK) return rc;
-    if ((rc = ensure(ctx, ctx->rm_dst, db)) != SM_OK) return rc;
-    {
-        StageTimer t_(ctx, ctx->stream, SM_STAGE_H2D, 1);
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->rm_src.p, bgr, sb, hipMemcpyHostToDevice, ctx->stream));
-    }
-    if ((rc = sm_image_measure_u8_batch_device(ctx, (const uint8_t*)ctx->rm_src.p, 1, 0, H, W, src_stride, w1, r1, w2,
-                                               r2, alpha, (double*)ctx->rm_dst.p)) != SM_OK)
-        return rc;
-    {
-        StageTimer t_(ctx, ctx->stream, SM_STAGE_D2H, 1);
-        HIP_TRY(ctx, hipMemcpyAsync(dst, ctx->rm_dst.p, db, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return SM_OK;
-}
-
-int sm_pyr_down_u8_batch_device(sm_ctx* ctx, const uint8_t* d_src, int nimg, size_t src_img_stride_bytes, int H, int W,
-                                int src_stride, int channels, uint8_t* d_dst, size_t dst_img_stride_bytes,
-                                int dst_stride)
-{
-    if (!ctx) return fail(nullptr, SM_E_ARG, "ctx is NULL");
-    int rc;
-    if ((rc = filter_image_check(ctx, "pyrDown", d_src, d_dst, nimg, H, W)) != SM_OK) return rc;
-    if (channels != 1 && channels != 3) return fail(ctx, SM_E_ARG, "pyrDown: channels %d (1 or 3)", channels);
-    const int dH = (H + 1) / 2, dW = (W + 1) / 2;
-    if (src_stride < W * channels || dst_stride < dW * channels)
-        return fail(ctx, SM_E_ARG, "pyrDown: row stride %d / %d < %d / %d", src_stride, dst_stride, W * channels,
-                    dW * channels);
-    if (nimg > 1 && (src_img_stride_bytes < filter_span(1, 0, H, W * channels, src_stride) ||
-                     dst_img_stride_bytes < filter_span(1, 0, dH, dW * channels, dst_stride)))
-        return fail(ctx, SM_E_ARG, "pyrDown: image stride %zu / %zu smaller than one image", src_img_stride_bytes,
-                    dst_img_stride_bytes);
-    if (nimg == 0) return SM_OK;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    smk::PyrArgs a{};
-    a.src = d_src, a.dst = d_dst, a.src_img_stride = src_img_stride_bytes, a.dst_img_stride = dst_img_stride_bytes;
-    a.H = H, a.W = W, a.dH = dH, a.dW = dW, a.src_stride = src_stride, a.dst_stride = dst_stride;
-    a.vec = ((uintptr_t)d_dst | (uintptr_t)dst_stride | (nimg > 1 ? dst_img_stride_bytes : 0)) % 4 == 0;
-    const dim3 grid(((dW * channels + 3) / 4 + 255) / 256, dH, nimg);
-    if (channels == 1)
-        hipLaunchKernelGGL(smk::k_pyr_down_u8<1>, grid, dim3(256), 0, ctx->stream, a);
-    else
-        hipLaunchKernelGGL(smk::k_pyr_down_u8<3>, grid, dim3(256), 0, ctx->stream, a);
-    HIP_TRY(ctx, hipGetLastError());
-    return SM_OK;
-}
-
-int sm_pyr_down_u8(sm_ctx* ctx, const uint8_t* src, int H, int W, int src_stride, int channels, uint8_t* dst)
-{
-    if (!ctx) return fail(nullptr, SM_E_ARG, "ctx is NULL");
-    int rc;
-    if ((rc = filter_image_check(ctx, "pyrDown", src, dst, 1, H, W)) != SM_OK) return rc;
-    if (channels != 1 && channels != 3) return fail(ctx, SM_E_ARG, "pyrDown: channels %d (1 or 3)", channels);
-    if (src_stride < W * channels) return fail(ctx, SM_E_ARG, "pyrDown: src_stride %d < %d", src_stride, W * channels);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const int dH = (H + 1) / 2, dW = (W + 1) / 2;
-    const size_t sb = (size_t)(H - 1) * src_stride + (size_t)W * channels, db = (size_t)dH * dW * channels;
-    if ((rc = ensure(ctx, ctx->rm_src, sb)) != SM_OK) return rc;
-    if ((rc = ensure(ctx, ctx->rm_dst, db)) != SM_OK) return rc;
-    {
-        StageTimer t_(ctx, ctx->stream, SM_STAGE_H2D, 1);
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->rm_src.p, src, sb, hipMemcpyHostToDevice, ctx->stream));
-    }
-    if ((rc = sm_pyr_down_u8_batch_device(ctx, (const uint8_t*)ctx->rm_src.p, 1, 0, H, W, src_stride, channels,
-                                          (uint8_t*)ctx->rm_dst.p, 0, dW * channels)) != SM_OK)
-        return rc;
-    {
-        StageTimer t_(ctx, ctx->stream, SM_STAGE_D2H, 1);
-        HIP_TRY(ctx, hipMemcpyAsync(dst, ctx->rm_dst.p, db, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return SM_OK;
-}
-
-// ---- point clouds: masked extraction and the ASCII PLY body (sm_cloud.hpp)
-namespace {
-
-struct CloudGeo {
-    size_t npx, nblk, rows_max;
-    int bpi;
-    double lo, hi;
-};
-
-int cloud_check(sm_ctx* ctx, const void* disp, int disp_type, const uint8_t* bgr, size_t img_stride, int bgr_stride,
-                int nimg, int H, int W, const double* Q, const sm_cloud_params* p, CloudGeo& g)
-{
-    if (!disp || !bgr || !Q || !p) return fail(ctx, SM_E_ARG, "cloud: a required pointer is NULL");
-    if (H <= 0 || W <= 0) return fail(ctx, SM_E_ARG, "cloud: empty map (%dx%d)", W, H);
-    if (disp_type != SM_DISP_S16 && disp_type != SM_DISP_F32)
-        return fail(ctx, SM_E_UNSUPPORTED, "cloud: disparity type %d not supported (int16 or float32)", disp_type);
-    if (nimg < 0 || nimg > 65535) return fail(ctx, SM_E_ARG, "cloud: nimg %d", nimg);
-    if ((size_t)H * (size_t)W > ((size_t)1 << 30))
-        return fail(ctx, SM_E_UNSUPPORTED, "cloud: %dx%d is more than 2^30 pixels", W, H);
-    if ((size_t)bgr_stride < 3 * (size_t)W || bgr_stride < 0)
-        return fail(ctx, SM_E_ARG, "cloud: bgr_stride %d smaller than a row of %d BGR pixels", bgr_stride, W);
-    if (nimg > 1 && img_stride < (size_t)(H - 1) * bgr_stride + 3 * (size_t)W)
-        return fail(ctx, SM_E_ARG, "cloud: bgr_img_stride_bytes %zu smaller than one image", img_stride);
-    if (p->lo_mode != SM_CLOUD_LO_NONE && p->lo_mode != SM_CLOUD_LO_VALUE && p->lo_mode != SM_CLOUD_LO_MIN)
-        return fail(ctx, SM_E_ARG, "cloud: lo_mode %d unknown", p->lo_mode);
-    if ((p->lo_mode == SM_CLOUD_LO_VALUE && std::isnan(p->lo)) || (p->has_hi && std::isnan(p->hi)))
-        return fail(ctx, SM_E_ARG, "cloud: a bound is NaN");
-    g.npx = (size_t)H * W;
-    g.bpi = (int)((g.npx + smk::CLOUD_BLOCK - 1) / smk::CLOUD_BLOCK);
-    g.nblk = (size_t)g.bpi * (size_t)nimg;
-    g.rows_max = g.npx * (size_t)nimg;
-    if (g.nblk > 0x7FFFFFFFull) return fail(ctx, SM_E_UNSUPPORTED, "cloud: %zu blocks of pixels in one call", g.nblk);
-    // numpy >= 2 compares a float32 map with the Python scalar rounded to float32; an int16 map
-    // compares as the numbers they are
-    g.lo = disp_type == SM_DISP_F32 ? (double)(float)p->lo : p->lo;
-    g.hi = disp_type == SM_DISP_F32 ? (double)(float)p->hi : p->hi;
-    return SM_OK;
-}
-
-// the three launches of the extraction (+ the maps' minima when asked for) on the ctx stream.
-// d_verts NULL: counts only.  The total is left in ctx->cl_off[g.nblk].
-int cloud_extract_enqueue(sm_ctx* ctx, const void* d_disp, int disp_type, const uint8_t* d_bgr, size_t img_stride,
-                          int bgr_stride, int nimg, int H, int W, const double* Q, const sm_cloud_params* p,
-                          const CloudGeo& g, size_t cap_rows, float* d_verts, uint8_t* d_colors, int64_t* d_counts)
-{
-    int rc;
-    if ((rc = ensure(ctx, ctx->cl_tot, g.nblk * 4)) != SM_OK) return rc;
-    if ((rc = ensure(ctx, ctx->cl_off, (g.nblk + 1) * 8)) != SM_OK) return rc;
-    smk::CloudArgs a{};
-    a.disp = d_disp, a.bgr = d_bgr, a.bgr_img_stride = img_stride;
-    std::memcpy(a.Q, Q, sizeof a.Q);
-    a.lo = g.lo, a.hi = g.hi;
-    a.tot = (uint32_t*)ctx->cl_tot.p, a.offs = (const uint64_t*)ctx->cl_off.p;
-    a.verts = d_verts, a.colors = d_colors, a.cap_rows = cap_rows;
-    a.H = H, a.W = W, a.bgr_stride = bgr_stride, a.bpi = g.bpi;
-    a.has_lo = p->lo_mode == SM_CLOUD_LO_VALUE, a.has_hi = p->has_hi != 0;
-    a.handle_missing = p->handle_missing != 0, a.zero_nonfinite = p->zero_nonfinite != 0;
-    const bool s16 = disp_type == SM_DISP_S16;
-    if (a.handle_missing || p->lo_mode == SM_CLOUD_LO_MIN) {
-        if ((rc = ensure(ctx, ctx->rp_min, (size_t)nimg * 8)) != SM_OK) return rc;
-        int* keys = (int*)ctx->rp_min.p;
-        HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)keys, 0x7FFFFFFF, nimg, ctx->stream));
-        const dim3 gm((unsigned)std::min<size_t>((g.npx + 255) / 256, 1024), nimg);
-        if (s16)
-            hipLaunchKernelGGL(smk::k_disp_min<int16_t>, gm, dim3(256), 0, ctx->stream, (const int16_t*)d_disp, keys, g.npx);
-        else
-            hipLaunchKernelGGL(smk::k_disp_min<float>, gm, dim3(256), 0, ctx->stream, (const float*)d_disp, keys, g.npx);
-        hipLaunchKernelGGL(smk::k_keys_to_float, dim3((nimg + 63) / 64), dim3(64), 0, ctx->stream, keys,
-                           (float*)(keys + nimg), nimg);
-        if (a.handle_missing) a.min_disp = (const float*)(keys + nimg);
-        if (p->lo_mode == SM_CLOUD_LO_MIN) a.lo_dev = (const float*)(keys + nimg);
-    }
-    const dim3 grid(g.bpi, nimg), blk(smk::CLOUD_BLOCK);
-    if (s16)
-        hipLaunchKernelGGL(smk::k_cloud_count<int16_t>, grid, blk, 0, ctx->stream, a);
-    else
-        hipLaunchKernelGGL(smk::k_cloud_count<float>, grid, blk, 0, ctx->stream, a);
-    hipLaunchKernelGGL(smk::k_scan_totals, dim3(1), dim3(smk::SCAN_BLOCK), 0, ctx->stream, (const uint32_t*)ctx->cl_tot.p,
-                       (uint64_t*)ctx->cl_off.p, g.nblk, (uint64_t*)nullptr);
-    if (d_counts)
-        hipLaunchKernelGGL(smk::k_seg_counts, dim3((nimg + 63) / 64), dim3(64), 0, ctx->stream,
-                           (const uint64_t*)ctx->cl_off.p, d_counts, nimg, (size_t)g.bpi);
-    if (d_verts) {
-        if (s16)
-            hipLaunchKernelGGL(smk::k_cloud_scatter<int16_t>, grid, blk, 0, ctx->stream, a);
-        else
-            hipLaunchKernelGGL(smk::k_cloud_scatter<float>, grid, blk, 0, ctx->stream, a);
-    }
-    HIP_TRY(ctx, hipGetLastError());
-    return SM_OK;
-}
-
-// blocks of CLOUD_BLOCK rows that n rows make (at least one, so that a total is always written)
-int ply_blocks(sm_ctx* ctx, size_t n, size_t& nb)
-{
-    nb = std::max<size_t>((n + smk::CLOUD_BLOCK - 1) / smk::CLOUD_BLOCK, 1);
-    if (nb > 0x7FFFFFFFull) return fail(ctx, SM_E_UNSUPPORTED, "ply: %zu rows in one call", n);
-    return SM_OK;
-}
-
-// the byte lengths and their scan (the total lands in ctx->ply_off[nb] and, when given, *d_nbytes),
-// then the rows themselves when d_out is given.  n_dev: the row count in device memory (n is its cap).
-int ply_enqueue(sm_ctx* ctx, const float* d_verts, const uint8_t* d_colors, size_t n, const uint64_t* n_dev,
-                bool measure, size_t cap_bytes, char* d_out, uint64_t* d_nbytes)
-{
-    size_t nb;
-    int rc;
-    if ((rc = ply_blocks(ctx, n, nb)) != SM_OK) return rc;
-    if ((rc = ensure(ctx, ctx->ply_tot, nb * 4)) != SM_OK) return rc;
-    if ((rc = ensure(ctx, ctx->ply_off, (nb + 1) * 8)) != SM_OK) return rc;
-    smk::PlyArgs a{};
-    a.verts = d_verts, a.colors = d_colors, a.n_dev = n_dev, a.n = n;
-    a.tot = (uint32_t*)ctx->ply_tot.p, a.offs = (const uint64_t*)ctx->ply_off.p;
-    a.out = d_out, a.cap_bytes = cap_bytes;
-    if (measure) {
-        hipLaunchKernelGGL(smk::k_ply_len, dim3((unsigned)nb), dim3(smk::CLOUD_BLOCK), 0, ctx->stream, a);
-        hipLaunchKernelGGL(smk::k_scan_totals, dim3(1), dim3(smk::SCAN_BLOCK), 0, ctx->stream,
-                           (const uint32_t*)ctx->ply_tot.p, (uint64_t*)ctx->ply_off.p, nb, d_nbytes);
-    }
-    if (d_out) {
-        if (ctx->tune_ply_stage >= 0)
-            hipLaunchKernelGGL(smk::k_ply_write_lds, dim3((unsigned)nb), dim3(smk::CLOUD_BLOCK), smk::PLY_LDS_BYTES,
-                               ctx->stream, a);
-        else
-            hipLaunchKernelGGL(smk::k_ply_write, dim3((unsigned)nb), dim3(smk::CLOUD_BLOCK), 0, ctx->stream, a);
-    }
-    HIP_TRY(ctx, hipGetLastError());
-    return SM_OK;
-}
-
-// host form: the map and its BGR image into the context's buffers
-int cloud_upload(sm_ctx* ctx, const void* disp, int disp_type, const uint8_t* bgr, int bgr_stride, int H, int W)
-{
-    const size_t npx = (size_t)H * W, ib = npx * (disp_type == SM_DISP_S16 ? 2 : 4);
-    const size_t cb = (size_t)(H - 1) * bgr_stride + 3 * (size_t)W;
-    int rc;
-    if ((rc = ensure(ctx, ctx->rp_in, ib)) != SM_OK) return rc;
-    if ((rc = ensure(ctx, ctx->rm_src, cb)) != SM_OK) return rc;
-    if ((rc = ensure(ctx, ctx->cl_verts, npx * 12)) != SM_OK) return rc;
-    if ((rc = ensure(ctx, ctx->cl_colors, npx * 3)) != SM_OK) return rc;
-    StageTimer t_(ctx, ctx->stream, SM_STAGE_H2D, 1);
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->rp_in.p, disp, ib, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->rm_src.p, bgr, cb, hipMemcpyHostToDevice, ctx->stream));
-    return SM_OK;
-}
-
-}  // namespace
-
-int sm_cloud_extract_batch_device(sm_ctx* ctx, const void* d_disp, int disp_type, const uint8_t* d_bgr,
-                                  size_t bgr_img_stride_bytes, int bgr_stride, int nimg, int H, int W, const double* Q,
-                                  const sm_cloud_params* p, size_t capacity_rows, float* d_verts, uint8_t* d_colors,
-                                  int64_t* d_counts)
-{
-    if (!ctx) return fail(nullptr, SM_E_ARG, "ctx is NULL");
-    CloudGeo g;
-    int rc;
-    if ((rc = cloud_check(ctx, d_disp, disp_type, d_bgr, bgr_img_stride_bytes, bgr_stride, nimg, H, W, Q, p, g)) != SM_OK)
-        return rc;
-    if ((d_verts == nullptr) != (d_colors == nullptr) || (!d_verts && capacity_rows))
-        return fail(ctx, SM_E_ARG, "cloud: d_verts and d_colors go together (both NULL with capacity 0: counts only)");
-    if (!d_verts && !d_counts) return fail(ctx, SM_E_ARG, "cloud: nothing to compute (no outputs and no counts)");
-    if (nimg == 0) return SM_OK;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return cloud_extract_enqueue(ctx, d_disp, disp_type, d_bgr, bgr_img_stride_bytes, bgr_stride, nimg, H, W, Q, p, g,
-                                 capacity_rows, d_verts, d_colors, d_counts);
-}
-
-int sm_cloud_extract(sm_ctx* ctx, const void* disp, int disp_type, const uint8_t* bgr, int bgr_stride, int H, int W,
-                     const double* Q, const sm_cloud_params* p, size_t capacity_rows, float* verts, uint8_t* colors,
-                     int64_t* count)
-{
-    if (!ctx) return fail(nullptr, SM_E_ARG, "ctx is NULL");
-    CloudGeo g;
-    int rc;
-    if ((rc = cloud_check(ctx, disp, disp_type, bgr, 0, bgr_stride, 1, H, W, Q, p, g)) != SM_OK) return rc;
-    if (!count || (capacity_rows && (!verts || !colors))) return fail(ctx, SM_E_ARG, "cloud: an output pointer is NULL");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if ((rc = cloud_upload(ctx, disp, disp_type, bgr, bgr_stride, H, W)) != SM_OK) return rc;
-    if ((rc = cloud_extract_enqueue(ctx, ctx->rp_in.p, disp_type, (const uint8_t*)ctx->rm_src.p, 0, bgr_stride, 1, H, W, Q,
-                                    p, g, g.npx, (float*)ctx->cl_verts.p, (uint8_t*)ctx->cl_colors.p, nullptr)) != SM_OK)
-        return rc;
-    uint64_t n = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(&n, (const uint64_t*)ctx->cl_off.p + g.nblk, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    *count = (int64_t)n;
-    if (n > capacity_rows)
-        return fail(ctx, SM_E_ARG, "cloud: %llu rows pass the mask, the capacity is %zu", (unsigned long long)n,
-                    capacity_rows);
-    if (n) {
-        StageTimer t_(ctx, ctx->stream, SM_STAGE_D2H, 1);
-        HIP_TRY(ctx, hipMemcpyAsync(verts, ctx->cl_verts.p, n * 12, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(colors, ctx->cl_colors.p, n * 3, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return SM_OK;
-}
-
-int sm_ply_format_device(sm_ctx* ctx, const float* d_verts, const uint8_t* d_colors, size_t n, size_t capacity_bytes,
-                         char* d_out, uint64_t* d_nbytes)
-{
-    if (!ctx) return fail(nullptr, SM_E_ARG, "ctx is NULL");
-    if (n && (!d_verts || !d_colors)) return fail(ctx, SM_E_ARG, "ply: d_verts / d_colors is NULL");
-    if (!d_out && (capacity_bytes || !d_nbytes))
-        return fail(ctx, SM_E_ARG, "ply: d_out NULL needs capacity 0 and d_nbytes (the size query)");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return ply_enqueue(ctx, d_verts, d_colors, n, nullptr, true, capacity_bytes, d_out, d_nbytes);
-}
-
-int sm_cloud_ply_batch_device(sm_ctx* ctx, const void* d_disp, int disp_type, const uint8_t* d_bgr,
-                              size_t bgr_img_stride_bytes, int bgr_stride, int nimg, int H, int W, const double* Q,
-                              const sm_cloud_params* p, size_t capacity_bytes, char* d_out, int64_t* d_counts,
-                              uint64_t* d_nbytes)
-{
-    if (!ctx) return fail(nullptr, SM_E_ARG, "ctx is NULL");
-    CloudGeo g;
-    int rc;
-    if ((rc = cloud_check(ctx, d_disp, disp_type, d_bgr, bgr_img_stride_bytes, bgr_stride, nimg, H, W, Q, p, g)) != SM_OK)
-        return rc;
-    if (nimg == 0) return fail(ctx, SM_E_ARG, "cloud: nimg 0");
-    if (!d_out && (capacity_bytes || !d_nbytes))
-        return fail(ctx, SM_E_ARG, "ply: d_out NULL needs capacity 0 and d_nbytes (the size query)");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if ((rc = ensure(ctx, ctx->cl_verts, g.rows_max * 12)) != SM_OK) return rc;
-    if ((rc = ensure(ctx, ctx->cl_colors, g.rows_max * 3)) != SM_OK) return rc;
-    if ((rc = cloud_extract_enqueue(ctx, d_disp, disp_type, d_bgr, bgr_img_stride_bytes, bgr_stride, nimg, H, W, Q, p, g,
-                                    g.rows_max, (float*)ctx->cl_verts.p, (uint8_t*)ctx->cl_colors.p, d_counts)) != SM_OK)
-        return rc;
-    return ply_enqueue(ctx, (const float*)ctx->cl_verts.p, (const uint8_t*)ctx->cl_colors.p, g.rows_max,
-                       (const uint64_t*)ctx->cl_off.p + g.nblk, true, capacity_bytes, d_out, d_nbytes);
-}
-
-int sm_cloud_ply(sm_ctx* ctx, const void* disp, int disp_type, const uint8_t* bgr, int bgr_stride, int H, int W,
-                 const double* Q, const sm_cloud_params* p, size_t capacity_bytes, char* out, int64_t* count,
-                 uint64_t* nbytes)
-{
-    if (!ctx) return fail(nullptr, SM_E_ARG, "ctx is NULL");
-    CloudGeo g;
-    int rc;
-    if ((rc = cloud_check(ctx, disp, disp_type, bgr, 0, bgr_stride, 1, H, W, Q, p, g)) != SM_OK) return rc;
-    if (!count || !nbytes || (capacity_bytes && !out)) return fail(ctx, SM_E_ARG, "cloud: an output pointer is NULL");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if ((rc = cloud_upload(ctx, disp, disp_type, bgr, bgr_stride, H, W)) != SM_OK) return rc;
-    if ((rc = cloud_extract_enqueue(ctx, ctx->rp_in.p, disp_type, (const uint8_t*)ctx->rm_src.p, 0, bgr_stride, 1, H, W, Q,
-                                    p, g, g.npx, (float*)ctx->cl_verts.p, (uint8_t*)ctx->cl_colors.p, nullptr)) != SM_OK)
-        return rc;
-    size_t nb;
-    if ((rc = ply_blocks(ctx, g.npx, nb)) != SM_OK) return rc;
-    const uint64_t* n_dev = (const uint64_t*)ctx->cl_off.p + g.nblk;
-    if ((rc = ply_enqueue(ctx, (const float*)ctx->cl_verts.p, (const uint8_t*)ctx->cl_colors.p, g.npx, n_dev, true, 0,
-                          nullptr, nullptr)) != SM_OK)
-        return rc;
-    uint64_t n = 0, nby = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(&n, n_dev, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(&nby, (const uint64_t*)ctx->ply_off.p + nb, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    *count = (int64_t)n;
-    *nbytes = nby;
-    if (nby > capacity_bytes)
-        return fail(ctx, SM_E_ARG, "ply: the body is %llu bytes, the capacity is %zu", (unsigned long long)nby,
-                    capacity_bytes);
-    if (nby) {
-        // the rows only: the lengths and their scan are still in place (ensure of a new buffer
-        // leaves the others alone)
-        if ((rc = ensure(ctx, ctx->cl_out, nby)) != SM_OK) return rc;
-        if ((rc = ply_enqueue(ctx, (const float*)ctx->cl_verts.p, (const uint8_t*)ctx->cl_colors.p, g.npx, n_dev, false,
-                              nby, (char*)ctx->cl_out.p, nullptr)) != SM_OK)
-            return rc;
-        StageTimer t_(ctx, ctx->stream, SM_STAGE_D2H, 1);
-        HIP_TRY(ctx, hipMemcpyAsync(out, ctx->cl_out.p, nby, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return SM_OK;
-}
-
-int sm_ply_format_host(const float* verts, const uint8_t* colors, size_t n, size_t capacity_bytes, char* out,
-                       uint64_t* nbytes)
-{
-    if (!nbytes || (n && (!verts || !colors)) || (capacity_bytes && !out))
-        return fail(nullptr, SM_E_ARG, "ply: a required pointer is NULL");
-    // rows in chunks, one thread a chunk: the lengths first, then every chunk writes at its offset
-    const size_t nt = std::max<size_t>(1, std::min<size_t>({(size_t)std::thread::hardware_concurrency(), 16, n / 32768}));
-    const size_t per = (n + nt - 1) / nt;
-    std::vector<uint64_t> len(nt, 0), at(nt + 1, 0);
-    auto span = [&](size_t t, bool write) {
-        const size_t r0 = std::min(n, t * per), r1 = std::min(n, r0 + per);
-        if (write) {
-            char* o = out + at[t];
-            for (size_t r = r0; r < r1; ++r) o += smk::ply_row<true>(verts + 3 * r, colors + 3 * r, o);
-        } else {
-            uint64_t s = 0;
-            for (size_t r = r0; r < r1; ++r) s += (uint64_t)smk::ply_row<false>(verts + 3 * r, colors + 3 * r, nullptr);
-            len[t] = s;
-        }
-    };
-    auto run = [&](bool write) {
-        std::vector<std::thread> th;
-        for (size_t t = 1; t < nt; ++t) th.emplace_back(span, t, write);
-        span(0, write);
-        for (auto& x : th) x.join();
-    };
-    run(false);
-    for (size_t t = 0; t < nt; ++t) at[t + 1] = at[t] + len[t];
-    *nbytes = at[nt];
-    if (at[nt] > capacity_bytes)
-        return fail(nullptr, SM_E_ARG, "ply: the body is %llu bytes, the capacity is %zu", (unsigned long long)at[nt],
-                    capacity_bytes);
-    run(true);
-    return SM_OK;
-}
-
-// ---- PNG output (sm_png.hpp)
-namespace {
-
-// the checks and the geometry of all three entry points (ctx NULL: the CPU twin)
-int png_setup(sm_ctx* ctx, const void* img, size_t img_stride, size_t row_stride, int nimg, int H, int W,
-              const sm_png_params* p, smk::PngArgs& a)
-{
-    if (!img || !p) return fail(ctx, SM_E_ARG, "png: a required pointer is NULL");
-    if (H <= 0 || W <= 0) return fail(ctx, SM_E_ARG, "png: empty image (%dx%d)", W, H);
-    if (nimg < 1 || nimg > 65535) return fail(ctx, SM_E_ARG, "png: nimg %d", nimg);
-    if (p->src_kind < SM_PNG_SRC_U8 || p->src_kind > SM_PNG_SRC_DISP_F32)
-        return fail(ctx, SM_E_ARG, "png: src_kind %d unknown", p->src_kind);
-    const bool disp = p->src_kind >= SM_PNG_SRC_DISP_I16;
-    if (p->src_kind == SM_PNG_SRC_U8 ? (p->channels != 1 && p->channels != 3) : p->channels != 1)
-        return fail(ctx, SM_E_ARG, "png: %d channels (uint8: 1 or 3; uint16 and disparity maps: 1)", p->channels);
-    if (p->filter < -1 || p->filter > 4) return fail(ctx, SM_E_ARG, "png: filter %d (-1 adaptive, 0..4)", p->filter);
-    if (disp && p->disp_mode != SM_PNG_DISP_KITTI && p->disp_mode != SM_PNG_DISP_LINEAR_U8)
-        return fail(ctx, SM_E_ARG, "png: disp_mode %d unknown", p->disp_mode);
-    const bool linear = disp && p->disp_mode == SM_PNG_DISP_LINEAR_U8;
-    if (linear && p->src_kind == SM_PNG_SRC_DISP_F32)
-        return fail(ctx, SM_E_UNSUPPORTED, "png: SM_PNG_DISP_LINEAR_U8 takes an int16 map");
-    if (linear && p->has_bounds && p->hi < p->lo) return fail(ctx, SM_E_ARG, "png: hi %d < lo %d", p->hi, p->lo);
-    const size_t esz = p->src_kind == SM_PNG_SRC_U8 ? 1 : p->src_kind == SM_PNG_SRC_DISP_F32 ? 4 : 2;
-    const size_t src_row = (size_t)W * esz * (size_t)p->channels;
-    if (row_stride < src_row) return fail(ctx, SM_E_ARG, "png: row_stride_bytes %zu smaller than a row (%zu)", row_stride, src_row);
-    if (nimg > 1 && img_stride < (size_t)(H - 1) * row_stride + src_row)
-        return fail(ctx, SM_E_ARG, "png: img_stride_bytes %zu smaller than one image", img_stride);
-    if (row_stride % esz || (nimg > 1 && img_stride % esz) || reinterpret_cast<uintptr_t>(img) % esz)
-        return fail(ctx, SM_E_ARG, "png: the image is not aligned to its %zu-byte samples", esz);
-    a = smk::PngArgs{};
-    a.img = static_cast<const uint8_t*>(img), a.img_stride = img_stride, a.row_stride = row_stride;
-    a.H = H, a.W = W;
-    a.kind = p->src_kind, a.channels = p->channels, a.keep = p->keep_channel_order != 0, a.filter = p->filter;
-    a.mode = disp ? p->disp_mode : 0;
-    a.lo = p->lo, a.hi = p->hi;
-    a.depth = (p->src_kind == SM_PNG_SRC_U16 || (disp && !linear)) ? 16 : 8;
-    a.out_channels = p->channels;
-    a.bpp = a.out_channels * a.depth / 8;
-    const uint64_t rowbytes = (uint64_t)W * a.bpp, stream = (rowbytes + 1) * (uint64_t)H;
-    if (stream >= (1ull << 31)) return fail(ctx, SM_E_UNSUPPORTED, "png: a filtered stream of %llu bytes (2^31 and more)", (unsigned long long)stream);
-    a.rowbytes = (uint32_t)rowbytes, a.stream_len = stream, a.stream_stride = (stream + 15) & ~15ull;
-    a.nseg = (uint32_t)((stream + smk::PNG_SEG - 1) / smk::PNG_SEG);
-    return SM_OK;
-}
-
-size_t png_bound_of(uint64_t stream, uint32_t nseg) { return (size_t)(57 + 6 + 17ull * nseg + stream); }
-
-}  // namespace
-
-size_t sm_png_bound(int H, int W, int channels, int depth)
-{
-    if (H <= 0 || W <= 0 || (channels != 1 && channels != 3) || (depth != 8 && depth != 16) || (channels == 3 && depth == 16))
-        return 0;
-    const uint64_t stream = ((uint64_t)W * channels * (depth / 8) + 1) * (uint64_t)H;
-    if (stream >= (1ull << 31)) return 0;
-    return png_bound_of(stream, (uint32_t)((stream + smk::PNG_SEG - 1) / smk::PNG_SEG));
-}
-
-int sm_png_encode_batch_device(sm_ctx* ctx, const void* d_img, size_t img_stride_bytes, size_t row_stride_bytes,
-                               int nimg, int H, int W, const sm_png_params* p, size_t capacity_bytes, uint8_t* d_out,
-                               uint64_t* d_nbytes)
-{
-    if (!ctx) return fail(nullptr, SM_E_ARG, "ctx is NULL");
-    smk::PngArgs a;
-    int rc;
-    if ((rc = png_setup(ctx, d_img, img_stride_bytes, row_stride_bytes, nimg, H, W, p, a)) != SM_OK) return rc;
-    if (!d_out && (capacity_bytes || !d_nbytes))
-        return fail(ctx, SM_E_ARG, "png: d_out NULL needs capacity 0 and d_nbytes (the size query)");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t nchunk = (size_t)nimg * a.nseg;
-    if ((rc = ensure(ctx, ctx->png_stream, (size_t)nimg * a.stream_stride)) != SM_OK) return rc;
-    if ((rc = ensure(ctx, ctx->png_slots, nchunk * smk::PNG_SLOT)) != SM_OK) return rc;
-    if ((rc = ensure(ctx, ctx->png_seg, nchunk * sizeof(smk::PngSegInfo))) != SM_OK) return rc;
-    if ((rc = ensure(ctx, ctx->png_off, nchunk * 8)) != SM_OK) return rc;
-    if ((rc = ensure(ctx, ctx->png_img, (size_t)nimg * sizeof(smk::PngImgInfo))) != SM_OK) return rc;
-    if (!d_nbytes) {
-        if ((rc = ensure(ctx, ctx->png_nb, (size_t)nimg * 8)) != SM_OK) return rc;
-        d_nbytes = (uint64_t*)ctx->png_nb.p;
-    }
-    a.stream = (uint8_t*)ctx->png_stream.p, a.slots = (uint8_t*)ctx->png_slots.p;
-    a.seginfo = (smk::PngSegInfo*)ctx->png_seg.p, a.offs = (uint64_t*)ctx->png_off.p;
-    a.imginfo = (smk::PngImgInfo*)ctx->png_img.p;
-    a.out = d_out, a.capacity = capacity_bytes, a.nbytes = d_nbytes;
-    const dim3 blk(smk::PNG_BLOCK);
-    if (a.kind == SM_PNG_SRC_DISP_I16 && a.mode == SM_PNG_DISP_LINEAR_U8 && !p->has_bounds) {
-        if ((rc = ensure(ctx, ctx->png_range, (size_t)nimg * 8)) != SM_OK) return rc;
-        int* keys = (int*)ctx->png_range.p;
-        HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)keys, 0x7FFFFFFF, 2 * (size_t)nimg, ctx->stream));
-        hipLaunchKernelGGL(smk::k_png_minmax, dim3(std::min(H, 64), nimg), blk, 0, ctx->stream, a, keys);
-        a.range = keys;
-    }
-    const dim3 fgrid((H + smk::PNG_FILTER_ROWS - 1) / smk::PNG_FILTER_ROWS, nimg);
-    if (a.rowbytes <= smk::PNG_MAX_ROW) {
-        const size_t flds = (size_t)(smk::PNG_FILTER_ROWS + 1) * ((a.rowbytes + 3u) & ~3u);
-        if (flds > 48 * 1024)  // above the default limit of dynamic LDS
-            HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(smk::k_png_filter<true>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)flds));
-        hipLaunchKernelGGL(smk::k_png_filter<true>, fgrid, blk, flds, ctx->stream, a);
-    } else {
-        hipLaunchKernelGGL(smk::k_png_filter<false>, fgrid, blk, 0, ctx->stream, a);
-    }
-    const size_t dlds = sizeof(smk::PngDeflateLds);
-    HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(smk::k_png_deflate),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)dlds));
-    hipLaunchKernelGGL(smk::k_png_deflate, dim3(a.nseg, nimg), dim3(smk::PNG_DBLOCK), dlds, ctx->stream, a);
-    hipLaunchKernelGGL(smk::k_png_assemble, dim3(nimg), blk, 0, ctx->stream, a);
-    if (d_out) hipLaunchKernelGGL(smk::k_png_scatter, dim3(a.nseg, nimg), blk, 0, ctx->stream, a);
-    HIP_TRY(ctx, hipGetLastError());
-    return SM_OK;
-}
-
-int sm_png_encode(sm_ctx* ctx, const void* img, size_t row_stride_bytes, int H, int W, const sm_png_params* p,
-                  size_t capacity_bytes, uint8_t* out, uint64_t* nbytes)
-{
-    if (!ctx) return fail(nullptr, SM_E_ARG, "ctx is NULL");
-    smk::PngArgs a;
-    int rc;
-    if ((rc = png_setup(ctx, img, 0, row_stride_bytes, 1, H, W, p, a)) != SM_OK) return rc;
-    if (!nbytes || (capacity_bytes && !out)) return fail(ctx, SM_E_ARG, "png: an output pointer is NULL");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t esz = a.kind == SM_PNG_SRC_U8 ? 1 : a.kind == SM_PNG_SRC_DISP_F32 ? 4 : 2;
-    const size_t ib = (size_t)(H - 1) * row_stride_bytes + (size_t)W * esz * a.channels;
-    const size_t bound = png_bound_of(a.stream_len, a.nseg);
-    if ((rc = ensure(ctx, ctx->png_in, ib)) != SM_OK) return rc;
-    if ((rc = ensure(ctx, ctx->png_out, bound)) != SM_OK) return rc;
-    if ((rc = ensure(ctx, ctx->png_nb, 8)) != SM_OK) return rc;
-    {
-        StageTimer t_(ctx, ctx->stream, SM_STAGE_H2D, 1);
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->png_in.p, img, ib, hipMemcpyHostToDevice, ctx->stream));
-    }
-    if ((rc = sm_png_encode_batch_device(ctx, ctx->png_in.p, 0, row_stride_bytes, 1, H, W, p, bound,
-                                         (uint8_t*)ctx->png_out.p, (uint64_t*)ctx->png_nb.p)) != SM_OK)
-        return rc;
-    uint64_t n = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(&n, ctx->png_nb.p, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    *nbytes = n;
-    if (n > capacity_bytes)
-        return fail(ctx, SM_E_ARG, "png: the file is %llu bytes, the capacity is %zu", (unsigned long long)n, capacity_bytes);
-    {
-        StageTimer t_(ctx, ctx->stream, SM_STAGE_D2H, 1);
-        HIP_TRY(ctx, hipMemcpyAsync(out, ctx->png_out.p, n, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return SM_OK;
-}
-
-int sm_png_encode_host(const void* img, size_t row_stride_bytes, int H, int W, const sm_png_params* p,
-                       size_t capacity_bytes, uint8_t* out, uint64_t* nbytes)
-{
-    smk::PngArgs a;
-    int rc;
-    if ((rc = png_setup(nullptr, img, 0, row_stride_bytes, 1, H, W, p, a)) != SM_OK) return rc;
-    if (!nbytes || (capacity_bytes && !out)) return fail(nullptr, SM_E_ARG, "png: an output pointer is NULL");
-    if (a.kind == SM_PNG_SRC_DISP_I16 && a.mode == SM_PNG_DISP_LINEAR_U8 && !p->has_bounds) {
-        int lo = 0x7FFFFFFF, hi = -0x7FFFFFFF;
-        for (int y = 0; y < H; ++y) {
-            const int16_t* row = reinterpret_cast<const int16_t*>(a.img + (size_t)y * row_stride_bytes);
-            for (int x = 0; x < W; ++x) lo = std::min(lo, (int)row[x]), hi = std::max(hi, (int)row[x]);
-        }
-        a.lo = lo, a.hi = hi;
-    }
-    std::vector<uint8_t> file;
-    smk::png_encode_host(a, file);
-    *nbytes = file.size();
-    if (file.size() > capacity_bytes)
-        return fail(nullptr, SM_E_ARG, "png: the file is %zu bytes, the capacity is %zu", file.size(), capacity_bytes);
-    std::memcpy(out, file.data(), file.size());
-    return SM_OK;
-}
-
-// ---- PNG input (sm_pngdec.hpp)
-namespace {
-
-thread_local int g_pd_host_path[2] = {0, 0};  // the last sm_png_decode_host: parallel, serial
-
-int pngdec_code(int status)
-{
-    if (status == smk::PD_OK) return SM_OK;
-    return (status >= smk::PD_E_INTERLACE && status <= smk::PD_E_SIZE) ? SM_E_UNSUPPORTED : SM_E_DATA;
-}
-
-int pngdec_fail(sm_ctx* ctx, int status, int index)
-{
-    const int code = pngdec_code(status);
-    if (index >= 0) return fail(ctx, code, "png decode: image %d: %s", index, smk::pngdec_message(status));
-    return fail(ctx, code, "png decode: %s", smk::pngdec_message(status));
-}
-
-// IHDR of a file in host memory: a status of the decoder
-int pngdec_info(const uint8_t* f, size_t n, smk::PdHdr& h)
-{
-    const uint8_t sig[8] = {0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A};
-    if (n < 8 || std::memcmp(f, sig, 8) != 0) return smk::PD_E_SIG;
-    if (n < 33) return smk::PD_E_TRUNC;
-    if (smk::pd_be32(f + 8) != 13u || std::memcmp(f + 12, "IHDR", 4) != 0) return smk::PD_E_IHDR;
-    return smk::pd_ihdr(f + 16, h);
-}
-
-// the checks and the geometry of all entry points (ctx NULL: the CPU twin)
-int pngdec_setup(sm_ctx* ctx, int nimg, int H, int W, const sm_pngdec_params* p, int fch, int fdepth, const void* out,
-                 size_t img_stride, size_t row_stride, smk::PdArgs& a)
-{
-    if (!p || !out) return fail(ctx, SM_E_ARG, "png decode: a required pointer is NULL");
-    if (nimg < 1 || nimg > 65535) return fail(ctx, SM_E_ARG, "png decode: nimg %d", nimg);
-    if (H < 1 || W < 1) return fail(ctx, SM_E_ARG, "png decode: empty image (%dx%d)", W, H);
-    if ((fch != 1 && fch != 3 && fch != 4) || (fdepth != 8 && fdepth != 16) || (fdepth == 16 && fch != 1))
-        return fail(ctx, SM_E_ARG, "png decode: file_channels %d at file_depth %d (1 at 8 or 16; 3 or 4 at 8)", fch, fdepth);
-    if (p->out_kind < SM_PNGDEC_U8 || p->out_kind > SM_PNGDEC_DISP_F32)
-        return fail(ctx, SM_E_ARG, "png decode: out_kind %d unknown", p->out_kind);
-    if (p->flags < -1 || p->flags > 1) return fail(ctx, SM_E_ARG, "png decode: flags %d (1, 0 or -1)", p->flags);
-    a = smk::PdArgs{};
-    a.kind = p->out_kind, a.keep = p->keep_channel_order != 0, a.inv_i16 = p->invalid_i16, a.inv_f32 = p->invalid_f32;
-    size_t opb;
-    if (p->out_kind == SM_PNGDEC_U8) {
-        if (p->flags == -1 && fdepth == 16)
-            return fail(ctx, SM_E_ARG, "png decode: flags -1 on a 16-bit file needs out_kind SM_PNGDEC_U16");
-        a.out_ch = p->flags == 1 ? 3 : p->flags == 0 ? 1 : (fch == 1 ? 1 : 3);
-        opb = (size_t)a.out_ch;
-    } else {
-        if (fdepth != 16 || fch != 1)
-            return fail(ctx, SM_E_UNSUPPORTED, "png decode: out_kind %d takes a 16-bit gray file, not %d channel(s) at depth %d",
-                        p->out_kind, fch, fdepth);
-        if (p->flags != -1) return fail(ctx, SM_E_ARG, "png decode: out_kind %d takes flags -1", p->out_kind);
-        if (p->out_kind != SM_PNGDEC_U16 && p->disp_mode != SM_PNG_DISP_KITTI)
-            return fail(ctx, SM_E_UNSUPPORTED, "png decode: only SM_PNG_DISP_KITTI maps are read back");
-        a.out_ch = 1;
-        opb = p->out_kind == SM_PNGDEC_DISP_F32 ? 4 : 2;
-    }
-    const size_t esz = p->out_kind == SM_PNGDEC_U8 ? 1 : opb;
-    if (row_stride < (size_t)W * opb)
-        return fail(ctx, SM_E_ARG, "png decode: row_stride_bytes %zu smaller than a row (%zu)", row_stride, (size_t)W * opb);
-    if (nimg > 1 && img_stride < (size_t)(H - 1) * row_stride + (size_t)W * opb)
-        return fail(ctx, SM_E_ARG, "png decode: img_stride_bytes %zu smaller than one image", img_stride);
-    if (row_stride % esz || (nimg > 1 && img_stride % esz) || reinterpret_cast<uintptr_t>(out) % esz)
-        return fail(ctx, SM_E_ARG, "png decode: the output is not aligned to its %zu-byte samples", esz);
-    a.nimg = nimg, a.H = H, a.W = W, a.file_ch = fch, a.depth = fdepth, a.bpp = fch * fdepth / 8;
-    const uint64_t rowbytes = (uint64_t)W * a.bpp, stream = (rowbytes + 1) * (uint64_t)H;
-    if (stream >= (1ull << 31))
-        return fail(ctx, SM_E_UNSUPPORTED, "png decode: a filtered stream of %llu bytes (2^31 and more)", (unsigned long long)stream);
-    a.rowbytes = (uint32_t)rowbytes, a.stream_len = stream, a.stream_stride = (stream + 15) & ~15ull;
-    a.nseg = (uint32_t)((stream + smk::PNG_SEG - 1) / smk::PNG_SEG);
-    a.maxpar = 2u * (uint32_t)((stream + smk::PNGDEC_CAP - 1) / smk::PNGDEC_CAP) + 4u;
-    a.out = static_cast<uint8_t*>(const_cast<void*>(out)), a.img_stride = img_stride, a.row_stride = row_stride;
-    return SM_OK;
-}
-
-}  // namespace
-
-const char* sm_pngdec_status_message(int status) { return smk::pngdec_message(status); }
-
-int sm_pngdec_status_code(int status) { return pngdec_code(status); }
-
-int sm_png_info(const uint8_t* file, size_t nbytes, int* H, int* W, int* channels, int* depth)
-{
-    if (!file || !H || !W || !channels || !depth) return fail(nullptr, SM_E_ARG, "png info: a required pointer is NULL");
-    smk::PdHdr h{};
-    const int st = pngdec_info(file, nbytes, h);
-    if (st) return pngdec_fail(nullptr, st, -1);
-    *H = (int)h.H, *W = (int)h.W, *channels = h.channels, *depth = h.depth;
-    return SM_OK;
-}
-
-int sm_png_decode_batch_device(sm_ctx* ctx, const uint8_t* d_files, const uint64_t* d_offsets, const uint64_t* d_sizes,
-                               int nimg, int H, int W, const sm_pngdec_params* p, void* d_out, size_t img_stride_bytes,
-                               size_t row_stride_bytes, int* d_status)
-{
-    if (!ctx) return fail(nullptr, SM_E_ARG, "ctx is NULL");
-    if (!d_files || !d_offsets || !d_sizes || !d_status) return fail(ctx, SM_E_ARG, "png decode: a required pointer is NULL");
-    smk::PdArgs a;
-    int rc;
-    if ((rc = pngdec_setup(ctx, nimg, H, W, p, p ? p->file_channels : 0, p ? p->file_depth : 0, d_out, img_stride_bytes,
-                           row_stride_bytes, a)) != SM_OK)
-        return rc;
-    if (p->max_chunks < 0) return fail(ctx, SM_E_ARG, "png decode: max_chunks %d", p->max_chunks);
-    a.files = d_files, a.offsets = d_offsets, a.sizes = d_sizes;
-    a.max_chunks = p->max_chunks ? (uint32_t)p->max_chunks : 2u * a.nseg + 64u;
-    a.max_file = p->max_file_bytes ? p->max_file_bytes : 2ull * png_bound_of(a.stream_len, a.nseg);
-    if (a.max_file > 0xFFFFFFFFull) a.max_file = 0xFFFFFFFFull;
-    a.zstride = (a.max_file + 15) & ~15ull;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t n = (size_t)nimg;
-    if ((rc = ensure(ctx, ctx->pd_img, n * sizeof(smk::PdImg))) != SM_OK) return rc;
-    if ((rc = ensure(ctx, ctx->pd_chunks, n * a.max_chunks * sizeof(smk::PdChunk))) != SM_OK) return rc;
-    if ((rc = ensure(ctx, ctx->pd_idat, n * a.max_chunks * sizeof(smk::PdIdat))) != SM_OK) return rc;
-    if ((rc = ensure(ctx, ctx->pd_cinfo, n * a.maxpar * sizeof(smk::PdChunkInfo))) != SM_OK) return rc;
-    if ((rc = ensure(ctx, ctx->pd_slots, n * a.maxpar * smk::PNGDEC_CAP)) != SM_OK) return rc;
-    if ((rc = ensure(ctx, ctx->pd_zbuf, n * a.zstride)) != SM_OK) return rc;
-    if ((rc = ensure(ctx, ctx->pd_stream, n * a.stream_stride)) != SM_OK) return rc;
-    if ((rc = ensure(ctx, ctx->pd_seg, n * a.nseg * sizeof(smk::PdChunkInfo))) != SM_OK) return rc;
-    const uint32_t ngrp = (uint32_t)((H + 63) / 64);  // row groups of the unfilter pass
-    if ((rc = ensure(ctx, ctx->pd_carry, n * ngrp * (size_t)W * 4)) != SM_OK) return rc;
-    a.img = (smk::PdImg*)ctx->pd_img.p, a.chunks = (smk::PdChunk*)ctx->pd_chunks.p, a.idat = (smk::PdIdat*)ctx->pd_idat.p;
-    a.cinfo = (smk::PdChunkInfo*)ctx->pd_cinfo.p, a.slots = (uint8_t*)ctx->pd_slots.p, a.zbuf = (uint8_t*)ctx->pd_zbuf.p;
-    a.stream = (uint8_t*)ctx->pd_stream.p, a.seg = (smk::PdChunkInfo*)ctx->pd_seg.p, a.carry = (uint32_t*)ctx->pd_carry.p;
-    const dim3 blk(smk::PNGDEC_BLOCK), wave(64);
-    const uint32_t cgrid = std::min<uint32_t>(a.max_chunks, 256u);
-    hipLaunchKernelGGL(smk::k_pngdec_parse, dim3(nimg), wave, 0, ctx->stream, a);
-    hipLaunchKernelGGL(smk::k_pngdec_crc, dim3(cgrid, nimg), blk, 0, ctx->stream, a);
-    hipLaunchKernelGGL(smk::k_pngdec_inflate, dim3(a.maxpar, nimg), wave, 0, ctx->stream, a);
-    hipLaunchKernelGGL(smk::k_pngdec_place, dim3(nimg), wave, 0, ctx->stream, a);
-    hipLaunchKernelGGL(smk::k_pngdec_compact, dim3(a.maxpar, nimg), blk, 0, ctx->stream, a);
-    hipLaunchKernelGGL(smk::k_pngdec_gather, dim3(cgrid, nimg), blk, 0, ctx->stream, a);
-    hipLaunchKernelGGL(smk::k_pngdec_inflate_serial, dim3(nimg), wave, 0, ctx->stream, a);
-    hipLaunchKernelGGL(smk::k_pngdec_adler, dim3(a.nseg, nimg), blk, 0, ctx->stream, a);
-    hipLaunchKernelGGL(smk::k_pngdec_verify, dim3(nimg), wave, 0, ctx->stream, a);
-    hipLaunchKernelGGL(smk::k_pngdec_unfilter, dim3(ngrp, nimg), blk, 0, ctx->stream, a);
-    hipLaunchKernelGGL(smk::k_pngdec_status, dim3((nimg + 255) / 256), blk, 0, ctx->stream, a, d_status);
-    HIP_TRY(ctx, hipGetLastError());
-    ctx->pd_last_nimg = nimg;
-    return SM_OK;
-}
-
-int sm_png_decode(sm_ctx* ctx, const uint8_t* file, size_t nbytes, const sm_pngdec_params* p, void* out,
-                  size_t row_stride_bytes, int* status)
-{
-    if (!ctx) return fail(nullptr, SM_E_ARG, "ctx is NULL");
-    if (!file || !p || !out) return fail(ctx, SM_E_ARG, "png decode: a required pointer is NULL");
-    if (status) *status = 0;
-    smk::PdHdr h{};
-    int st = pngdec_info(file, nbytes, h);
-    if (st) {
-        if (status) *status = st;
-        return pngdec_fail(ctx, st, -1);
-    }
-    sm_pngdec_params q = *p;
-    if (!q.file_channels) q.file_channels = h.channels;
-    if (!q.file_depth) q.file_depth = h.depth;
-    {  // the chunks the walk on the device can meet: counted here, every length checked first
-        size_t pos = 8, nc = 0;
-        while (nbytes - pos >= 12) {
-            const uint32_t len = smk::pd_be32(file + pos);
-            ++nc;
-            if ((uint64_t)len > nbytes - pos - 12) break;
-            pos += 12 + (size_t)len;
-        }
-        q.max_chunks = (int)std::min<size_t>(nc + 1, 0x7FFFFFFF);
-    }
-    q.max_file_bytes = nbytes;
-    smk::PdArgs a;
-    int rc;
-    if ((rc = pngdec_setup(ctx, 1, (int)h.H, (int)h.W, &q, q.file_channels, q.file_depth, out, 0, row_stride_bytes, a)) != SM_OK)
-        return rc;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t opb = a.kind == SM_PNGDEC_U8 ? (size_t)a.out_ch : a.kind == SM_PNGDEC_DISP_F32 ? 4 : 2;
-    const size_t drow = (size_t)h.W * opb;
-    if ((rc = ensure(ctx, ctx->pd_in, nbytes)) != SM_OK) return rc;
-    if ((rc = ensure(ctx, ctx->pd_tab, 16)) != SM_OK) return rc;
-    if ((rc = ensure(ctx, ctx->pd_out, drow * h.H)) != SM_OK) return rc;
-    if ((rc = ensure(ctx, ctx->pd_status, 4)) != SM_OK) return rc;
-    const uint64_t tab[2] = {0, (uint64_t)nbytes};
-    {
-        StageTimer t_(ctx, ctx->stream, SM_STAGE_H2D, 1);
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->pd_in.p, file, nbytes, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->pd_tab.p, tab, 16, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // tab lives on this frame
-    }
-    const uint64_t* dtab = (const uint64_t*)ctx->pd_tab.p;
-    if ((rc = sm_png_decode_batch_device(ctx, (const uint8_t*)ctx->pd_in.p, dtab, dtab + 1, 1, (int)h.H, (int)h.W, &q,
-                                         ctx->pd_out.p, 0, drow, (int*)ctx->pd_status.p)) != SM_OK)
-        return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(&st, ctx->pd_status.p, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (status) *status = st;
-    if (st) return pngdec_fail(ctx, st, -1);
-    {
-        StageTimer t_(ctx, ctx->stream, SM_STAGE_D2H, 1);
-        HIP_TRY(ctx, hipMemcpy2DAsync(out, row_stride_bytes, ctx->pd_out.p, drow, drow, h.H, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return SM_OK;
-}
-
-int sm_png_decode_host(const uint8_t* file, size_t nbytes, const sm_pngdec_params* p, void* out, size_t row_stride_bytes,
-                       int* status)
-{
-    if (!file || !p || !out) return fail(nullptr, SM_E_ARG, "png decode: a required pointer is NULL");
-    if (status) *status = 0;
-    g_pd_host_path[0] = g_pd_host_path[1] = 0;
-    smk::PdHdr h{};
-    int st = pngdec_info(file, nbytes, h);
-    if (!st) {
-        const int fch = p->file_channels ? p->file_channels : h.channels, fdepth = p->file_depth ? p->file_depth : h.depth;
-        smk::PdArgs a;
-        int rc;
-        if ((rc = pngdec_setup(nullptr, 1, (int)h.H, (int)h.W, p, fch, fdepth, out, 0, row_stride_bytes, a)) != SM_OK) return rc;
-        const uint64_t off = 0, size = nbytes;
-        a.files = file, a.offsets = &off, a.sizes = &size;
-        uint32_t path = 0;
-        st = smk::pngdec_host(a, path);
-        if (path == smk::PD_PATH_PARALLEL) g_pd_host_path[0] = 1;
-        if (path == smk::PD_PATH_SERIAL) g_pd_host_path[1] = 1;
-    }
-    if (status) *status = st;
-    return st ? pngdec_fail(nullptr, st, -1) : SM_OK;
-}
-
-int sm_png_decode_stats(sm_ctx* ctx, int* n_parallel, int* n_serial)
-{
-    if (!n_parallel || !n_serial) return fail(ctx, SM_E_ARG, "png decode: a required pointer is NULL");
-    *n_parallel = *n_serial = 0;
-    if (!ctx) {
-        *n_parallel = g_pd_host_path[0], *n_serial = g_pd_host_path[1];
-        return SM_OK;
-    }
-    if (ctx->pd_last_nimg <= 0) return SM_OK;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    std::vector<smk::PdImg> v((size_t)ctx->pd_last_nimg);
-    HIP_TRY(ctx, hipMemcpyAsync(v.data(), ctx->pd_img.p, v.size() * sizeof(smk::PdImg), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    for (const smk::PdImg& im : v) {
-        if (im.path == smk::PD_PATH_PARALLEL) ++*n_parallel;
-        if (im.path == smk::PD_PATH_SERIAL) ++*n_serial;
-    }
-    return SM_OK;
-}
-
-// ---- JPEG input (sm_jpegdec.hpp)
-namespace {
-
-thread_local int g_jd_host_nsub = 0;  // lanes the last sm_jpeg_decode_host would have used
-
-int jpegdec_code(int status)
-{
-    if (status == smk::JD_OK) return SM_OK;
-    return smk::jpegdec_unsupported(status) ? SM_E_UNSUPPORTED : SM_E_DATA;
-}
-
-int jpegdec_fail(sm_ctx* ctx, int status)
-{
-    return fail(ctx, jpegdec_code(status), "jpeg decode: %s", smk::jpegdec_message(status));
-}
-
-// the checks and the geometry of all entry points (ctx NULL: the CPU twin)
-int jpegdec_setup(sm_ctx* ctx, int nimg, int H, int W, const sm_jpegdec_params* p, int fch, int sub, const void* out,
-                  size_t img_stride, size_t row_stride, smk::JdArgs& a)
-{
-    if (!p || !out) return fail(ctx, SM_E_ARG, "jpeg decode: a required pointer is NULL");
-    if (nimg < 1 || nimg > 65535) return fail(ctx, SM_E_ARG, "jpeg decode: nimg %d", nimg);
-    if (H < 1 || W < 1 || H > 65535 || W > 65535) return fail(ctx, SM_E_ARG, "jpeg decode: image size %dx%d", W, H);
-    if ((size_t)H * (size_t)W >= (1u << 28))
-        return fail(ctx, SM_E_UNSUPPORTED, "jpeg decode: %s", smk::jpegdec_message(smk::JD_E_SIZE));
-    if (!((fch == 1) || (fch == 3 && (sub == 444 || sub == 422 || sub == 420))))
-        return fail(ctx, SM_E_ARG, "jpeg decode: file_channels %d with subsampling %d (1, or 3 with 444, 422 or 420)", fch, sub);
-    if (p->flags < -1 || p->flags > 1) return fail(ctx, SM_E_ARG, "jpeg decode: flags %d (1, 0 or -1)", p->flags);
-    a = smk::JdArgs{};
-    a.nimg = nimg, a.H = H, a.W = W, a.ncomp = fch;
-    a.hs = fch == 3 && sub != 444 ? 2 : 1, a.vs = fch == 3 && sub == 420 ? 2 : 1;
-    a.out_ch = p->flags == 1 ? 3 : p->flags == 0 ? 1 : fch;
-    a.y_only = a.out_ch == 1 || fch == 1, a.keep = p->keep_channel_order != 0;
-    const size_t opb = (size_t)a.out_ch;
-    if (row_stride < (size_t)W * opb)
-        return fail(ctx, SM_E_ARG, "jpeg decode: row_stride_bytes %zu smaller than a row (%zu)", row_stride, (size_t)W * opb);
-    if (nimg > 1 && img_stride < (size_t)(H - 1) * row_stride + (size_t)W * opb)
-        return fail(ctx, SM_E_ARG, "jpeg decode: img_stride_bytes %zu smaller than one image", img_stride);
-    smk::jd_geometry(a);
-    a.out = static_cast<uint8_t*>(const_cast<void*>(out)), a.img_stride = img_stride, a.row_stride = row_stride;
-    return SM_OK;
-}
-
-}  // namespace
-
-const char* sm_jpegdec_status_message(int status) { return smk::jpegdec_message(status); }
-
-int sm_jpegdec_status_code(int status) { return jpegdec_code(status); }
-
-size_t sm_jpeg_desc_bytes(void) { return sizeof(smk::JdDesc); }
-
-int sm_jpeg_parse(const uint8_t* file, size_t nbytes, void* desc, int* status)
-{
-    if (!file || !desc) return fail(nullptr, SM_E_ARG, "jpeg parse: a required pointer is NULL");
-    smk::JdDesc d;
-    const int st = smk::jd_parse(file, nbytes, d);
-    std::memcpy(desc, &d, sizeof d);
-    if (status) *status = st;
-    return st ? jpegdec_fail(nullptr, st) : SM_OK;
-}
-
-int sm_jpeg_info(const uint8_t* file, size_t nbytes, int* H, int* W, int* channels, int* subsampling)
-{
-    if (!file || !H || !W || !channels || !subsampling) return fail(nullptr, SM_E_ARG, "jpeg info: a required pointer is NULL");
-    smk::JdDesc d;
-    const int st = smk::jd_parse(file, nbytes, d);
-    if (st) return jpegdec_fail(nullptr, st);
-    *H = (int)d.H, *W = (int)d.W, *channels = d.ncomp, *subsampling = smk::jd_subsampling(d);
-    return SM_OK;
-}
-
-int sm_jpeg_decode_batch_device(sm_ctx* ctx, const uint8_t* d_files, const uint64_t* d_offsets, const uint64_t* d_sizes,
-                                int nimg, int H, int W, const sm_jpegdec_params* p, void* d_out, size_t img_stride_bytes,
-                                size_t row_stride_bytes, int* d_status)
-{
-    if (!ctx) return fail(nullptr, SM_E_ARG, "ctx is NULL");
-    if (!d_files || !d_offsets || !d_sizes || !d_status || !p || !p->d_desc)
-        return fail(ctx, SM_E_ARG, "jpeg decode: a required pointer is NULL");
-    smk::JdArgs a;
-    int rc;
-    if ((rc = jpegdec_setup(ctx, nimg, H, W, p, p->file_channels, p->subsampling, d_out, img_stride_bytes, row_stride_bytes,
-                            a)) != SM_OK)
-        return rc;
-    if (p->max_file_bytes < 1 || p->max_file_bytes > smk::JD_MAX_FILE)
-        return fail(ctx, SM_E_ARG, "jpeg decode: max_file_bytes %llu (1 .. 2^28 - 1)", (unsigned long long)p->max_file_bytes);
-    a.files = d_files, a.offsets = d_offsets, a.sizes = d_sizes, a.desc = static_cast<const smk::JdDesc*>(p->d_desc);
-    a.max_file = (uint32_t)p->max_file_bytes;
-    a.iv_cap = a.nmcu;
-    a.lane_cap = (a.max_file + smk::JD_SUBSEQ - 1) / smk::JD_SUBSEQ + a.nmcu + 1;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t n = (size_t)nimg, ivn = n * (a.iv_cap + 1), ln = n * a.lane_cap;
-    const size_t coef_bytes = n * a.nmcu * a.bpm * 64 * sizeof(int16_t);
-    if ((rc = ensure(ctx, ctx->jd_img, n * sizeof(smk::JdImg))) != SM_OK) return rc;
-    if ((rc = ensure(ctx, ctx->jd_iv, 3 * ivn * sizeof(uint32_t))) != SM_OK) return rc;
-    if ((rc = ensure(ctx, ctx->jd_state, 3 * ln * sizeof(smk::JdState))) != SM_OK) return rc;
-    if ((rc = ensure(ctx, ctx->jd_lane, ln * (3 * sizeof(uint32_t) + 1))) != SM_OK) return rc;
-    if ((rc = ensure(ctx, ctx->jd_coef, coef_bytes)) != SM_OK) return rc;
-    if ((rc = ensure(ctx, ctx->jd_planes, n * a.plane_stride)) != SM_OK) return rc;
-    a.img = (smk::JdImg*)ctx->jd_img.p;
-    a.ibeg = (uint32_t*)ctx->jd_iv.p, a.iend = a.ibeg + ivn, a.ilane = a.iend + ivn;
-    a.start = (smk::JdState*)ctx->jd_state.p, a.exit_a = a.start + ln, a.exit_b = a.exit_a + ln;
-    a.nblk = (uint32_t*)ctx->jd_lane.p, a.lane_iv = a.nblk + ln, a.gpre = a.lane_iv + ln, a.flag = (uint8_t*)(a.gpre + ln);
-    a.coef = (int16_t*)ctx->jd_coef.p, a.planes = (uint8_t*)ctx->jd_planes.p;
-    HIP_TRY(ctx, hipMemsetAsync(ctx->jd_coef.p, 0, coef_bytes, ctx->stream));
-    const dim3 blk(smk::JD_BLOCK);
-    const uint32_t lgrid = (a.lane_cap + smk::JD_BLOCK - 1) / smk::JD_BLOCK;
-    const uint32_t nblocks = a.nmcu * a.bpm;
-    hipLaunchKernelGGL(smk::k_jpeg_split, dim3(nimg), blk, 0, ctx->stream, a);
-    hipLaunchKernelGGL(smk::k_jpeg_sync_a, dim3(lgrid, nimg), blk, 0, ctx->stream, a);
-    hipLaunchKernelGGL(smk::k_jpeg_sync_b, dim3(lgrid, nimg), blk, 0, ctx->stream, a);
-    hipLaunchKernelGGL(smk::k_jpeg_sync_loop, dim3(nimg), dim3(smk::JD_LOOP_BLOCK), 0, ctx->stream, a);
-    hipLaunchKernelGGL(smk::k_jpeg_write, dim3(lgrid, nimg), blk, 0, ctx->stream, a);
-    hipLaunchKernelGGL(smk::k_jpeg_dc, dim3(a.y_only ? 1 : a.ncomp, nimg), blk, 0, ctx->stream, a);
-    hipLaunchKernelGGL(smk::k_jpeg_idct, dim3((nblocks + 31) / 32, nimg), blk, 0, ctx->stream, a);
-    hipLaunchKernelGGL(smk::k_jpeg_color, dim3((W + smk::JD_BLOCK - 1) / smk::JD_BLOCK, (H + 1) / 2, nimg), blk, 0, ctx->stream, a);
-    hipLaunchKernelGGL(smk::k_jpeg_status, dim3((nimg + smk::JD_BLOCK - 1) / smk::JD_BLOCK), blk, 0, ctx->stream, a, d_status);
-    HIP_TRY(ctx, hipGetLastError());
-    ctx->jd_last_nimg = nimg;
-    return SM_OK;
-}
-
-int sm_jpeg_decode(sm_ctx* ctx, const uint8_t* file, size_t nbytes, const sm_jpegdec_params* p, void* out,
-                   size_t row_stride_bytes, int* status)
-{
-    if (!ctx) return fail(nullptr, SM_E_ARG, "ctx is NULL");
-    if (!file || !p || !out) return fail(ctx, SM_E_ARG, "jpeg decode: a required pointer is NULL");
-    if (status) *status = 0;
-    smk::JdDesc d;
-    int st = smk::jd_parse(file, nbytes, d);
-    if (st) {
-        if (status) *status = st;
-        return jpegdec_fail(ctx, st);
-    }
-    sm_jpegdec_params q = *p;
-    if (!q.file_channels) q.file_channels = d.ncomp, q.subsampling = smk::jd_subsampling(d);
-    q.max_file_bytes = nbytes;
-    smk::JdArgs a;
-    int rc;
-    if ((rc = jpegdec_setup(ctx, 1, (int)d.H, (int)d.W, &q, q.file_channels, q.subsampling, out, 0, row_stride_bytes, a)) != SM_OK)
-        return rc;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t drow = (size_t)d.W * a.out_ch;
-    if ((rc = ensure(ctx, ctx->jd_in, nbytes)) != SM_OK) return rc;
-    if ((rc = ensure(ctx, ctx->jd_desc, sizeof d)) != SM_OK) return rc;
-    if ((rc = ensure(ctx, ctx->jd_tab, 16)) != SM_OK) return rc;
-    if ((rc = ensure(ctx, ctx->jd_out, drow * d.H)) != SM_OK) return rc;
-    if ((rc = ensure(ctx, ctx->jd_status, 4)) != SM_OK) return rc;
-    const uint64_t tab[2] = {0, (uint64_t)nbytes};
-    {
-        StageTimer t_(ctx, ctx->stream, SM_STAGE_H2D, 1);
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->jd_in.p, file, nbytes, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->jd_desc.p, &d, sizeof d, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->jd_tab.p, tab, 16, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // d and tab live on this frame
-    }
-    q.d_desc = ctx->jd_desc.p;
-    const uint64_t* dtab = (const uint64_t*)ctx->jd_tab.p;
-    if ((rc = sm_jpeg_decode_batch_device(ctx, (const uint8_t*)ctx->jd_in.p, dtab, dtab + 1, 1, (int)d.H, (int)d.W, &q,
-                                          ctx->jd_out.p, 0, drow, (int*)ctx->jd_status.p)) != SM_OK)
-        return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(&st, ctx->jd_status.p, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (status) *status = st;
-    if (st) return jpegdec_fail(ctx, st);
-    {
-        StageTimer t_(ctx, ctx->stream, SM_STAGE_D2H, 1);
-        HIP_TRY(ctx, hipMemcpy2DAsync(out, row_stride_bytes, ctx->jd_out.p, drow, drow, d.H, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return SM_OK;
-}
-
-int sm_jpeg_decode_host(const uint8_t* file, size_t nbytes, const sm_jpegdec_params* p, void* out, size_t row_stride_bytes,
-                        int* status)
-{
-    if (!file || !p || !out) return fail(nullptr, SM_E_ARG, "jpeg decode: a required pointer is NULL");
-    if (status) *status = 0;
-    g_jd_host_nsub = 0;
-    smk::JdDesc d;
-    int st = smk::jd_parse(file, nbytes, d);
-    if (!st) {
-        const int fch = p->file_channels ? p->file_channels : d.ncomp;
-        const int sub = p->file_channels ? p->subsampling : smk::jd_subsampling(d);
-        smk::JdArgs a;
-        int rc;
-        if ((rc = jpegdec_setup(nullptr, 1, (int)d.H, (int)d.W, p, fch, sub, out, 0, row_stride_bytes, a)) != SM_OK) return rc;
-        const uint64_t off = 0, size = nbytes;
-        a.files = file, a.offsets = &off, a.sizes = &size, a.desc = &d, a.max_file = (uint32_t)nbytes;
-        uint32_t nsub = 0;
-        st = smk::jpegdec_host(a, nsub);
-        g_jd_host_nsub = (int)nsub;
-    }
-    if (status) *status = st;
-    return st ? jpegdec_fail(nullptr, st) : SM_OK;
-}
-
-int sm_jpeg_decode_stats(sm_ctx* ctx, int* n_subsequences, int* n_sync_rounds)
-{
-    if (!n_subsequences || !n_sync_rounds) return fail(ctx, SM_E_ARG, "jpeg decode: a required pointer is NULL");
-    *n_subsequences = *n_sync_rounds = 0;
-    if (!ctx) {
-        *n_subsequences = g_jd_host_nsub;
-        return SM_OK;
-    }
-    if (ctx->jd_last_nimg <= 0) return SM_OK;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    std::vector<smk::JdImg> v((size_t)ctx->jd_last_nimg);
-    HIP_TRY(ctx, hipMemcpyAsync(v.data(), ctx->jd_img.p, v.size() * sizeof(smk::JdImg), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    for (const smk::JdImg& im : v) {
-        *n_subsequences += (int)im.nsub;
-        *n_sync_rounds = std::max(*n_sync_rounds, (int)im.rounds);
-    }
-    return SM_OK;
 }
 
 int sm_bm_default_params(int num_disparities, int block_size, sm_bm_params* out)
