@@ -783,6 +783,11 @@ int sm_set_debug_flags(sm_ctx* ctx, int flags);
  *                      128 disparities, all pairs of a group in one launch), -1 a launch of its
  *                      own between the sweeps.  The same results and repair counters either way;
  *                      other chains (5 paths, u16 costs, row bands) always use the launch.
+ *   SM_TUNE_HOP_EPOCH  (tests) v in 1..65535 sets the epoch counter whose low 16 bits tag the
+ *                      fused sweeps' boundary granules to v, once: the next sweep launch uses
+ *                      v + 1, and the launch after 65535 clears the granules and restarts at 1.
+ *                      v must be no smaller than the counter is (tags of later epochs would
+ *                      otherwise read as fresh); 0 changes nothing.
  * Returns SM_E_ARG for an unknown key or value. */
 #define SM_TUNE_EW_LANES 1
 #define SM_TUNE_SWEEP_NCW 2
@@ -800,6 +805,7 @@ int sm_set_debug_flags(sm_ctx* ctx, int flags);
 #define SM_TUNE_PLY_STAGE 14
 #define SM_TUNE_EW_START 15
 #define SM_TUNE_EW_PATCH 16
+#define SM_TUNE_HOP_EPOCH 17
 int sm_set_tuning(sm_ctx* ctx, int key, int value);
 
 /* Last error text of ctx (or of the calling thread when ctx == NULL). */

@@ -1046,6 +1046,7 @@ class Engine:
     TUNE_PLY_STAGE = 14
     TUNE_EW_START = 15
     TUNE_EW_PATCH = 16
+    TUNE_HOP_EPOCH = 17
 
     def set_tuning(self, key: int, value: int):
         """Launch-shape knob (include/stereo_match_amd.h sm_set_tuning); 0 = automatic."""
