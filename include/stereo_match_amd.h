@@ -808,6 +808,43 @@ int sm_set_debug_flags(sm_ctx* ctx, int flags);
 #define SM_TUNE_HOP_EPOCH 17
 int sm_set_tuning(sm_ctx* ctx, int key, int value);
 
+/* ---- MC-CNN fast matching cost: two gray images to the float32 cost volume
+ * sm_aggregate_cost_f32[_device] takes.  The network: L (1..6) convolutions 3x3, stride 1, zero
+ * padding 1, 64 feature maps, ReLU after every layer but the last; the 64 features of a pixel
+ * scaled to unit length; plane d of the volume at (y, x) is minus the dot product of image a's
+ * features at x and image b's at x - (min_disparity + d), NaN where that column is outside the
+ * image.  Every value is one fixed chain of fused multiply-adds, so the device and the *_host
+ * functions (plain C++, no context, no device) give the same bits.
+ *
+ * Weights: w[0] float32 [64][1][3][3], w[i] [64][64][3][3], b[i] [64] (the layout of torch's
+ * conv2d).  Images: uint8 gray, n of them image_stride bytes apart with rows row_stride bytes
+ * apart; each is normalised to zero mean and unit (unbiased) standard deviation, and a constant
+ * image fails the call with SM_E_ARG.  H * W < 2^24.  Feature maps: float32 [n][H][W][64]
+ * (channel last); device feature pointers (d_feat, d_feat_a, d_feat_b) must be 16-byte aligned
+ * (SM_E_ARG otherwise).  Volumes: float32 [n][D][H][W], D in 1..256, any min_disparity.  The
+ * device entry points run on the context's stream; the features wait for the images' sums (the
+ * check for a constant image) and for the upload of the grey-level tables, the join does not
+ * wait.  The scratch buffers belong to the context: a caller that moves it to another stream
+ * between calls orders the two streams itself. */
+int sm_mccnn_set_weights(sm_ctx* ctx, int L, const float* const* w, const float* const* b);
+int sm_mccnn_features_device(sm_ctx* ctx, const uint8_t* d_gray, int n, size_t image_stride, int H, int W,
+                             size_t row_stride, float* d_feat);
+int sm_mccnn_join_device(sm_ctx* ctx, const float* d_feat_a, const float* d_feat_b, int n, int H, int W, int D,
+                         int min_disparity, float* d_vol);
+int sm_mccnn_volume_device(sm_ctx* ctx, const uint8_t* d_a, const uint8_t* d_b, int n, size_t image_stride, int H,
+                           int W, size_t row_stride, int D, int min_disparity, float* d_vol);
+/* Host pointers in and out (images packed: rows W bytes, images H * W bytes apart). */
+int sm_mccnn_features(sm_ctx* ctx, const uint8_t* gray, int n, int H, int W, float* feat);
+int sm_mccnn_join(sm_ctx* ctx, const float* feat_a, const float* feat_b, int n, int H, int W, int D,
+                  int min_disparity, float* vol);
+int sm_mccnn_volume(sm_ctx* ctx, const uint8_t* a, const uint8_t* b, int n, int H, int W, int D, int min_disparity,
+                    float* vol);
+/* The CPU twin of the two steps. */
+int sm_mccnn_features_host(int L, const float* const* w, const float* const* b, const uint8_t* gray, int n,
+                           size_t image_stride, int H, int W, size_t row_stride, float* feat);
+int sm_mccnn_join_host(const float* feat_a, const float* feat_b, int n, int H, int W, int D, int min_disparity,
+                       float* vol);
+
 /* Last error text of ctx (or of the calling thread when ctx == NULL). */
 const char* sm_last_error(sm_ctx* ctx);
 

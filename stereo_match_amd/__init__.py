@@ -22,6 +22,8 @@ Public surface (mirrors the reference / OpenCV names the reference uses):
 * :func:`imread`, :func:`imdecode`, :func:`imdecode_batch`, :func:`imdecode_host`,
   :func:`read_disparity_png`, :func:`decode_disparity_png` — PNG files read back (``cv2.imread``,
   ``disparity_test.py:79-80``, ``mapTo3D.py:78-79``), decoded on the device
+* :class:`McCnnFast` — the mc-cnn *fast* matching cost, images to the float32 cost volume of
+  :meth:`StereoSGBM.computeFromCost` (``mc_cnn/script.py:9``, ``mapTo3D_mc_cnn.py:71``)
 
 All compute runs in ``libstereo_match_amd.so`` (HIP, gfx950) through the
 C-ABI in ``include/stereo_match_amd.h``; there is no CPU fallback.
@@ -41,6 +43,8 @@ from .png import (decode_disparity_png, encode_disparity_png, imdecode, imdecode
                   imencode_png_batch, imencode_png_host, imread, imwrite, read_disparity_png, write_disparity_png)
 from . import filters
 from .filters import gaussian_filter, image_measure, pyrDown
+from . import mccnn
+from .mccnn import McCnnFast
 
 __all__ = [
     "compute_disparity", "matcher_from_settings", "StereoSGBM", "StereoSGBM_create", "createRightMatcher",
@@ -54,5 +58,6 @@ __all__ = [
     "encode_disparity_png", "imread", "imdecode", "imdecode_batch", "imdecode_host", "read_disparity_png",
     "decode_disparity_png",
     "filters", "gaussian_filter", "image_measure", "pyrDown",
+    "mccnn", "McCnnFast",
 ]
 __version__ = "0.1.0"

@@ -233,6 +233,22 @@ _SIGS = {
     "sm_jpeg_decode_stats": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_int), _c.POINTER(_c.c_int)]),
     "sm_jpegdec_status_message": (_c.c_char_p, [_c.c_int]),
     "sm_jpegdec_status_code": (_c.c_int, [_c.c_int]),
+    "sm_mccnn_set_weights": (_c.c_int, [_c.c_void_p, _c.c_int, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_void_p)]),
+    "sm_mccnn_features_device": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_size_t, _c.c_int, _c.c_int,
+                                            _c.c_size_t, _c.c_void_p]),
+    "sm_mccnn_join_device": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
+                                        _c.c_int, _c.c_void_p]),
+    "sm_mccnn_volume_device": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_size_t, _c.c_int,
+                                          _c.c_int, _c.c_size_t, _c.c_int, _c.c_int, _c.c_void_p]),
+    "sm_mccnn_features": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p]),
+    "sm_mccnn_join": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
+                                 _c.c_int, _c.c_void_p]),
+    "sm_mccnn_volume": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
+                                   _c.c_int, _c.c_void_p]),
+    "sm_mccnn_features_host": (_c.c_int, [_c.c_int, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_void_p), _c.c_void_p,
+                                          _c.c_int, _c.c_size_t, _c.c_int, _c.c_int, _c.c_size_t, _c.c_void_p]),
+    "sm_mccnn_join_host": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
+                                      _c.c_void_p]),
     "sm_bm_default_params": (_c.c_int, [_c.c_int, _c.c_int, _c.POINTER(SmBmParams)]),
     "sm_bm_right_matcher_params": (_c.c_int, [_c.POINTER(SmBmParams), _c.POINTER(SmBmParams)]),
     "sm_bm_compute": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int,
@@ -404,6 +420,32 @@ def jpeg_decode_host(buf, prm: "SmJpegDecParams", out: np.ndarray):
     if rc != SM_OK:
         _raise(rc, None)
     return out
+
+
+def _ptr_array(arrays):
+    """A C array of the arrays' data pointers (float32, contiguous; the caller keeps them alive)."""
+    return (ctypes.c_void_p * len(arrays))(*[a.ctypes.data for a in arrays])
+
+
+def mccnn_features_host(weights, biases, gray: np.ndarray, image_stride: int, row_stride: int, n: int, H: int, W: int):
+    """sm_mccnn_features_host: the CPU twin's feature maps [n, H, W, 64] of n gray images inside
+    ``gray`` (a uint8 array; images / rows ``image_stride`` / ``row_stride`` bytes apart)."""
+    feat = np.empty((n, H, W, 64), np.float32)
+    rc = load().sm_mccnn_features_host(len(weights), _ptr_array(weights), _ptr_array(biases), gray.ctypes.data, n,
+                                       image_stride, H, W, row_stride, feat.ctypes.data)
+    if rc != SM_OK:
+        _raise(rc, None)
+    return feat
+
+
+def mccnn_join_host(fa: np.ndarray, fb: np.ndarray, D: int, min_disparity: int) -> np.ndarray:
+    """sm_mccnn_join_host: the CPU twin's volume [n, D, H, W] of feature maps [n, H, W, 64]."""
+    n, H, W = fa.shape[:3]
+    vol = np.empty((n, D, H, W), np.float32)
+    rc = load().sm_mccnn_join_host(fa.ctypes.data, fb.ctypes.data, n, H, W, D, min_disparity, vol.ctypes.data)
+    if rc != SM_OK:
+        _raise(rc, None)
+    return vol
 
 
 def volume_scale(scale) -> float:
@@ -839,6 +881,44 @@ class Engine:
         self._check(self._lib.sm_png_encode_batch_device(
             self.ctx, ctypes.c_void_p(d_img), img_stride, row_stride, nimg, H, W, ctypes.byref(prm), capacity_bytes,
             ctypes.c_void_p(d_out or None), ctypes.c_void_p(d_nbytes or None)))
+
+    def mccnn_set_weights(self, weights, biases):
+        """sm_mccnn_set_weights: float32 arrays w0 [64,1,3,3], w1.. [64,64,3,3] and b0.. [64]."""
+        self._check(self._lib.sm_mccnn_set_weights(self.ctx, len(weights), _ptr_array(weights), _ptr_array(biases)))
+
+    def mccnn_features(self, gray: np.ndarray) -> np.ndarray:
+        """sm_mccnn_features: contiguous uint8 [n, H, W] -> float32 [n, H, W, 64]."""
+        n, H, W = gray.shape
+        feat = np.empty((n, H, W, 64), np.float32)
+        self._check(self._lib.sm_mccnn_features(self.ctx, gray.ctypes.data, n, H, W, feat.ctypes.data))
+        return feat
+
+    def mccnn_join(self, fa: np.ndarray, fb: np.ndarray, D: int, min_disparity: int) -> np.ndarray:
+        """sm_mccnn_join: feature maps [n, H, W, 64] -> the volume [n, D, H, W]."""
+        n, H, W = fa.shape[:3]
+        vol = np.empty((n, D, H, W), np.float32)
+        self._check(self._lib.sm_mccnn_join(self.ctx, fa.ctypes.data, fb.ctypes.data, n, H, W, D, min_disparity,
+                                            vol.ctypes.data))
+        return vol
+
+    def mccnn_volume(self, a: np.ndarray, b: np.ndarray, D: int, min_disparity: int) -> np.ndarray:
+        """sm_mccnn_volume: contiguous uint8 [n, H, W] images -> the volume [n, D, H, W]."""
+        n, H, W = a.shape
+        vol = np.empty((n, D, H, W), np.float32)
+        self._check(self._lib.sm_mccnn_volume(self.ctx, a.ctypes.data, b.ctypes.data, n, H, W, D, min_disparity,
+                                              vol.ctypes.data))
+        return vol
+
+    def mccnn_features_device(self, d_gray: int, n: int, image_stride: int, H: int, W: int, row_stride: int, d_feat: int):
+        self._check(self._lib.sm_mccnn_features_device(self.ctx, d_gray, n, image_stride, H, W, row_stride, d_feat))
+
+    def mccnn_join_device(self, d_fa: int, d_fb: int, n: int, H: int, W: int, D: int, min_disparity: int, d_vol: int):
+        self._check(self._lib.sm_mccnn_join_device(self.ctx, d_fa, d_fb, n, H, W, D, min_disparity, d_vol))
+
+    def mccnn_volume_device(self, d_a: int, d_b: int, n: int, image_stride: int, H: int, W: int, row_stride: int,
+                            D: int, min_disparity: int, d_vol: int):
+        self._check(self._lib.sm_mccnn_volume_device(self.ctx, d_a, d_b, n, image_stride, H, W, row_stride, D,
+                                                     min_disparity, d_vol))
 
     def nlm_denoise(self, src: np.ndarray, h: float, template_window: int, search_window: int,
                     dst: np.ndarray = None) -> np.ndarray:

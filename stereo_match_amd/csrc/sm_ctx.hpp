@@ -1,6 +1,6 @@
 // sm_ctx.hpp — the host-side context of the C-ABI, shared by its translation units
 // (sm_api.hip: the matcher core; sm_api_image.hip, sm_api_cloud.hip, sm_api_png.hip,
-// sm_api_jpeg.hip: the leaf subsystems).  Host code only: every kernel header is compiled
+// sm_api_jpeg.hip, sm_api_mccnn.hip: the leaf subsystems).  Host code only: every kernel header is compiled
 // in exactly one unit, so none is included here.  fail, ensure, get_event, stage_in,
 // stage_out and check_sweep_errors are defined once, in sm_api.hip.
 #pragma once
@@ -81,6 +81,16 @@ struct sm_ctx {
         DevBuf img, iv, state, lane, coef, planes, in, desc, tab, out, status;
         int last_nimg = 0;
     } jpegdec;
+    // MC-CNN matching cost (sm_mccnn.hpp): the packed weights and biases of the L layers, the
+    // images' sums and grey-level tables (and their host copies, which outlive the transfers),
+    // the two ping-pong feature maps of one image, the feature maps of the volume entry points;
+    // images, features and volume of the host-pointer calls
+    struct {
+        DevBuf w, b, sums, tab, ping, pong, fa, fb, in_a, in_b, vol;
+        std::vector<unsigned long long> sums_host;
+        std::vector<float> tab_host;
+        int L = 0;
+    } mccnn;
     struct { DevBuf a; } filter;  // image_measure: the first Gaussian's result, [img][H][W] float64
     DevBuf wls_num, wls_den, wls_inter, wls_w, wls_disp[2], wls_out;  // WLS scratch
     DevBuf wls_R, wls_IT;         // WLS: Thomas pivots / elimination factors of every pass
