@@ -51,7 +51,11 @@ extern "C" {
  * and normalised exactly as OpenCV does (P1<=0 -> 2, ...). */
 typedef struct sm_params {
     int min_disparity;
-    int num_disparities; /* > 0, multiple of 16 (OpenCV asserts this); cost volumes: any 1..256 */
+    /* > 0, multiple of 16 (OpenCV asserts this), up to 512; cost volumes: any 1..512.  Above 256:
+     * gray input, block_size <= 11 and costs in the fast domain only (BGR input and the int16
+     * path stop at 256, as sm_bm_params does), on the per-direction engine;
+     * everything else is SM_E_UNSUPPORTED with the reason in sm_last_error */
+    int num_disparities;
     int block_size;      /* SADWindowSize; <= 0 -> 5 */
     int P1, P2;
     int disp12_max_diff;
@@ -124,7 +128,7 @@ int sm_compute_batch_device_cn(sm_ctx* ctx, const uint8_t* d_left, const uint8_t
  * one as float32 (1, D, H, W) at mapTo3D_mc_cnn.py:71 and feeds its
  * disparities to the WLS filter, :81-100).  cost: float32 [D][H][W], d-major,
  * plane d = cost of left x against right x - (min_disparity + d); D must equal
- * p->num_disparities, any value in 1..256 (OpenCV's multiple-of-16 rule is
+ * p->num_disparities, any value in 1..512 (OpenCV's multiple-of-16 rule is
  * StereoSGBM's own; mc-cnn's -disp_max 228 volume has 228 planes: the kernels
  * run the next multiple of 16 with pad planes that never win).
  * Costs are quantised q = rint((c + offset) * scale)

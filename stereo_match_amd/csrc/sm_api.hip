@@ -28,6 +28,7 @@
 #include "sm_ctx.hpp"
 #include "sm_cost.hpp"
 #include "sm_paths.hpp"
+#include "sm_deep_host.hpp"
 #include "sm_post.hpp"
 #include "sm_wls.hpp"
 #include "sm_speckle.hpp"
@@ -106,6 +107,10 @@ constexpr int DBG_NO_FALLBACK = (int)0x80000000u;
 // flags only the ablation build (SM_ABLATIONS) accepts: timing switches whose results are
 // wrong (1, 2, 4 in the path kernels; 1 << 24..26 in the sweeps; 1 << 28, 1 << 29 in the WLS
 // smoother; 1 << 31), the row-WTA kernel (16, 32), k_sweep2 (128, 1 << 27), the hybrid engine
+// numDisparities: the fused sweeps, the row bands, the wide path and the ablation engines stop at
+// kSweepMaxD; above it (to kMaxD) only the per-direction engine's sm_deep.hpp instances run
+constexpr int kSweepMaxD = 256, kMaxD = 512;
+constexpr int kNotDeepFlags = DBG_SWEEP1 | DBG_SWEEP8 | DBG_ROW | DBG_SWEEP_V2 | DBG_HYBRID | DBG_COST_TILE;
 constexpr int kAblationFlags = 1 | 2 | 4 | DBG_STORE_W | DBG_ROW | DBG_SWEEP_V2 | DBG_SWEEP2_NW | DBG_HYBRID |
                                (7 << 24) | DBG_FGS_NO_SWEEP | DBG_FGS_NO_MEM | DBG_NO_FALLBACK;
 
@@ -196,7 +201,12 @@ int normalize(sm_ctx* ctx, const sm_params* p, int H, int W, Norm& n, int cn = 1
     } else if (n.D <= 0 || n.D % 16 != 0) {
         return fail(ctx, SM_E_ARG, "numDisparities must be a positive multiple of 16 (got %d)", n.D);
     }
-    if (n.D > 256) return fail(ctx, SM_E_UNSUPPORTED, "numDisparities %d > 256 not built", n.Dv);
+    if (n.D > kMaxD) return fail(ctx, SM_E_UNSUPPORTED, "numDisparities %d > %d not built", n.Dv, kMaxD);
+    // 256 < D <= 512 runs on the per-direction engine alone (sm_deep.hpp): no fused sweeps
+    if (n.D > kSweepMaxD && ctx && (ctx->dbg_flags & kNotDeepFlags))
+        return fail(ctx, SM_E_UNSUPPORTED,
+                    "numDisparities %d > %d runs on the per-direction engine only (debug flags %d select another)", n.Dv,
+                    kSweepMaxD, ctx->dbg_flags & kNotDeepFlags);
     n.maxD = n.minD + n.Dv;
     n.bs = p->block_size > 0 ? p->block_size : 5;
     n.ftzero = std::max(p->pre_filter_cap, 15) | 1;
@@ -233,6 +243,11 @@ int normalize(sm_ctx* ctx, const sm_params* p, int H, int W, Norm& n, int cn = 1
             return fail(ctx, SM_E_UNSUPPORTED, "cost-volume mode needs P2 <= %d", 16383 - smk::VOL_CMAX);
     }
     if (!n.wide && (n.P1 > 16383 || n.P2 > 16383)) return fail(ctx, SM_E_UNSUPPORTED, "P1/P2 too large");
+    if (n.wide && n.D > kSweepMaxD)
+        return fail(ctx, SM_E_UNSUPPORTED,
+                    "numDisparities %d > %d needs gray input, blockSize <= 11 and costs in the fast domain "
+                    "(the int16 path for BGR input, blockSize > 11 or larger costs stops at %d)",
+                    n.Dv, kSweepMaxD, kSweepMaxD);
     n.minX1 = std::max(n.maxD, 0);
     n.maxX1 = W + std::min(n.minD, 0);
     n.width1 = n.maxX1 - n.minX1;
@@ -329,28 +344,29 @@ bool use_cost8(const sm_ctx* ctx, const Norm& n)
 {
     return n.cost == SM_COST_CENSUS && !(ctx->dbg_flags & DBG_NO_C8) && n.D <= 256;
 }
+// numDisparities > 256: sm_deep.hpp's instances of the per-direction engine, which always read
+// their costs from a volume (census: the u8 Hamming volume k_census_cost writes)
+bool deep(const Norm& n) { return n.D > kSweepMaxD; }
+bool deep_cost8(const Norm& n) { return deep(n) && n.cost == SM_COST_CENSUS; }
 hipStream_t stream_b(const sm_ctx* ctx)
 {
     return ctx->wta_override ? ctx->wta_override : overlap(ctx) ? ctx->side : ctx->stream;
 }
 
 // ---- stream A: path aggregation -------------------------------------------
-template <int DPLV, bool CENSUS, int VL, bool H16 = false>
-int launch_paths_t(sm_ctx* ctx, const Norm& n, const Geo& g, BufSet& bs, int dirset)
+// the arguments and the grid of a per-direction launch with horizontal lines of lanesh lanes and
+// vertical-family lines of vl lanes
+dim3 paths_args(const sm_ctx* ctx, const Norm& n, const Geo& g, const BufSet& bs, int dirset, int lanesh, int vl,
+                smk::PathsArgs& pa)
 {
-    using LT = typename std::conditional<CENSUS, uint8_t, uint16_t>::type;
-    constexpr int D = 16 * DPLV;
-    constexpr bool WIDE = D % 64 == 0 && !H16;
-    constexpr int LANESH = WIDE ? 64 : 16;
-    constexpr int DPLH = D / LANESH;
-    smk::PathsArgs pa{};
+    pa = smk::PathsArgs{};
     pa.cl = (const uint64_t*)bs.census[0].p;
     pa.cr = (const uint64_t*)bs.census[1].p;
     pa.census_pair = g.census_pair;
     pa.cost = (const uint16_t*)bs.cost.p;
     pa.cost_pair = g.cost_pair;
     pa.cost8 = nullptr;
-    if (use_cost8(ctx, n)) {
+    if (use_cost8(ctx, n) || deep_cost8(n)) {
         pa.cost8 = (const uint8_t*)bs.cost.p;
         pa.cost_pair = g.vol;
     }
@@ -366,14 +382,14 @@ int launch_paths_t(sm_ctx* ctx, const Norm& n, const Geo& g, BufSet& bs, int dir
     pa.P1 = n.P1;
     pa.P2 = n.P2;
     pa.dbg = ctx->dbg_flags;
-    const int lines_per_wg = 4 * (64 / LANESH);
+    const int lines_per_wg = 4 * (64 / lanesh);
     pa.hblocks = row_mode(ctx, n) ? 0 : (g.H + lines_per_wg - 1) / lines_per_wg;
     // DIRS_ALL: every direction; DIRS_EW: E and W only (sweep engine); DIRS_EW_UP:
     // E, W and the up family NE, N, NW (hybrid engine, slots 2..4)
     pa.nv = dirset == DIRS_ALL ? n.ndirs - 2 : dirset == DIRS_EW ? 0 : 3;
     const int k0 = dirset == DIRS_EW_UP ? 3 : 0;
     int blocks = 0;
-    constexpr int LPWV = 64 / VL;
+    const int LPWV = 64 / vl;
     for (int k = 0; k < pa.nv; k++) {
         const int dx = kVdx[k0 + k];
         pa.v_dx[k] = dx;
@@ -386,7 +402,19 @@ int launch_paths_t(sm_ctx* ctx, const Norm& n, const Geo& g, BufSet& bs, int dir
         blocks += ((pa.v_nlines[k] + 8 * LPWV - 1) / (8 * LPWV)) * 2;
     }
     for (int k = pa.nv; k <= 6; k++) pa.v_blk_start[k] = blocks;
-    dim3 grid(2 * pa.hblocks + blocks, g.G);
+    return dim3(2 * pa.hblocks + blocks, g.G);
+}
+
+template <int DPLV, bool CENSUS, int VL, bool H16 = false>
+int launch_paths_t(sm_ctx* ctx, const Norm& n, const Geo& g, BufSet& bs, int dirset)
+{
+    using LT = typename std::conditional<CENSUS, uint8_t, uint16_t>::type;
+    constexpr int D = 16 * DPLV;
+    constexpr bool WIDE = D % 64 == 0 && !H16;
+    constexpr int LANESH = WIDE ? 64 : 16;
+    constexpr int DPLH = D / LANESH;
+    smk::PathsArgs pa;
+    dim3 grid = paths_args(ctx, n, g, bs, dirset, LANESH, VL, pa);
     if (ctx->fb_guard) {  // guarded fallback: a small grid that walks every block if the sweep gave up
         pa.guard = ctx->fb_guard;
         pa.nblocks = (int)grid.x;
@@ -406,6 +434,35 @@ int launch_paths_t(sm_ctx* ctx, const Norm& n, const Geo& g, BufSet& bs, int dir
 }
 
 // ---- stream B: WTA (or the fused horizontal + WTA row kernel) ----------------
+void wta_args(const sm_ctx* ctx, const Norm& n, const Geo& g, const BufSet& bs, smk::WtaArgs& wa)
+{
+    wa = smk::WtaArgs{};
+    wa.L = (const uint8_t*)bs.L.p;
+    wa.slot_bytes = g.slot_bytes;
+    wa.L_pair_bytes = g.L_pair;
+    // in-sweep E/W lines (5 paths): S = the patched partial alone; the guarded fallback reads
+    // every direction's volume
+    const bool part_only = g.lines && !ctx->fb_guard;
+    wa.nslots = part_only ? 0 : g.hybrid ? hybrid_slots(n) : n.ndirs;
+    wa.part = (g.hybrid || part_only) ? (const uint16_t*)bs.part.p : nullptr;  // hybrid: S + SE + SW partial
+    wa.part_pair = g.vol;
+    wa.H = g.H;
+    wa.W = g.W;
+    wa.width1 = n.width1;
+    wa.D = n.D;
+    wa.Dv = n.Dv;
+    wa.minD = n.minD;
+    wa.minX1 = n.minX1;
+    wa.uniq = n.uniq;
+    wa.disp12 = n.disp12;
+    wa.disp = (int16_t*)bs.raw.p;
+    wa.wta = ctx->wta_dst;
+    wa.lane8 = n.ndirs == 5;
+    wa.skip = ctx->fb_guard ? nullptr : ctx->wta_skip;
+}
+
+enum { DISPATCH_PATHS = 0, DISPATCH_WTA = 1, DISPATCH_HORIZONTAL = 2, DISPATCH_HYBRID = 3 };
+
 #ifndef WTA_NT
 #define WTA_NT 1024  // threads per k_wta workgroup (one image row each)
 #endif
@@ -450,29 +507,8 @@ int launch_wta_t(sm_ctx* ctx, const Norm& n, const Geo& g, BufSet& bs)
         }
     }
 #endif
-    smk::WtaArgs wa{};
-    wa.L = (const uint8_t*)bs.L.p;
-    wa.slot_bytes = g.slot_bytes;
-    wa.L_pair_bytes = g.L_pair;
-    // in-sweep E/W lines (5 paths): S = the patched partial alone; the guarded fallback reads
-    // every direction's volume
-    const bool part_only = g.lines && !ctx->fb_guard;
-    wa.nslots = part_only ? 0 : g.hybrid ? hybrid_slots(n) : n.ndirs;
-    wa.part = (g.hybrid || part_only) ? (const uint16_t*)bs.part.p : nullptr;  // hybrid: S + SE + SW partial
-    wa.part_pair = g.vol;
-    wa.H = g.H;
-    wa.W = g.W;
-    wa.width1 = n.width1;
-    wa.D = n.D;
-    wa.Dv = n.Dv;
-    wa.minD = n.minD;
-    wa.minX1 = n.minX1;
-    wa.uniq = n.uniq;
-    wa.disp12 = n.disp12;
-    wa.disp = (int16_t*)bs.raw.p;
-    wa.wta = ctx->wta_dst;
-    wa.lane8 = n.ndirs == 5;
-    wa.skip = ctx->fb_guard ? nullptr : ctx->wta_skip;
+    smk::WtaArgs wa;
+    wta_args(ctx, n, g, bs, wa);
     dim3 grid(g.H, g.G);
     const size_t smem = (size_t)g.W * (ctx->wta_dst ? 10 : 8) + 16;
     if (smem > kRowLds)
@@ -495,6 +531,45 @@ int launch_wta_t(sm_ctx* ctx, const Norm& n, const Geo& g, BufSet& bs)
     return SM_OK;
 }
 
+// numDisparities > 256 (sm_deep.hip): all-direction launches of the per-direction engine only
+template <int... U>
+bool deep_paths_any(std::integer_sequence<int, U...>, int dpl, bool u8, dim3 grid, hipStream_t st, const smk::PathsArgs& pa)
+{
+    return (smk::deep_unit_paths<U>(dpl, u8, grid, st, pa) || ...);
+}
+template <int... U>
+bool deep_wta_any(std::integer_sequence<int, U...>, int dpl, bool u8, dim3 grid, size_t smem, hipStream_t st,
+                  const smk::WtaArgs& wa)
+{
+    return (smk::deep_unit_wta<U>(dpl, u8, grid, smem, st, wa) || ...);
+}
+
+int launch_deep(sm_ctx* ctx, const Norm& n, const Geo& g, BufSet& bs, int what)
+{
+    const bool u8 = n.cost == SM_COST_CENSUS;
+    const auto units = std::make_integer_sequence<int, smk::kDeepUnits>{};
+    bool built = false;
+    if (what == DISPATCH_WTA) {
+        smk::WtaArgs wa;
+        wta_args(ctx, n, g, bs, wa);
+        const size_t smem = (size_t)g.W * (ctx->wta_dst ? 10 : 8) + 16;
+        if (smem > kRowLds)
+            return fail(ctx, SM_E_UNSUPPORTED, "width %d: the WTA row kernel's %zu B of LDS exceed %zu%s", g.W, smem,
+                        kRowLds, ctx->wta_dst ? " (with the WTA index output)" : "");
+        StageTimer t(ctx, stream_b(ctx), SM_STAGE_WTA, g.G);
+        built = deep_wta_any(units, n.dpl, u8, dim3(g.H, g.G), smem, stream_b(ctx), wa);
+    } else if (what == DISPATCH_PATHS && !ctx->fb_guard) {
+        smk::PathsArgs pa;
+        const dim3 grid = paths_args(ctx, n, g, bs, DIRS_ALL, 16, 16, pa);
+        StageTimer t(ctx, ctx->stream, SM_STAGE_PATHS, g.G);
+        built = deep_paths_any(units, n.dpl, u8, grid, ctx->stream, pa);
+    }
+    if (!built) return fail(ctx, SM_E_UNSUPPORTED, "numDisparities %d not built", n.D);
+    HIP_TRY(ctx, hipGetLastError());
+    return SM_OK;
+}
+
+
 template <int DPLV, bool CENSUS>
 int launch_paths_dpl(sm_ctx* ctx, const Norm& n, const Geo& g, BufSet& bs, int dirset)
 {
@@ -514,12 +589,11 @@ int launch_paths_dpl(sm_ctx* ctx, const Norm& n, const Geo& g, BufSet& bs, int d
     return launch_paths_t<DPLV, CENSUS, 16, true>(ctx, n, g, bs, dirset);
 }
 
-enum { DISPATCH_PATHS = 0, DISPATCH_WTA = 1, DISPATCH_HORIZONTAL = 2, DISPATCH_HYBRID = 3 };
-
 int dispatch(sm_ctx* ctx, const Norm& n, const Geo& g, BufSet& bs, int what)
 {
     const bool census = n.cost == SM_COST_CENSUS;
     const int h = what == DISPATCH_HORIZONTAL ? DIRS_EW : what == DISPATCH_HYBRID ? DIRS_EW_UP : DIRS_ALL;
+    if (deep(n)) return launch_deep(ctx, n, g, bs, what);
     switch (n.dpl) {
 #define CASE(k)                                                                                               \
     case k:                                                                                                   \
@@ -558,6 +632,7 @@ bool use_hybrid(const sm_ctx* ctx, const Norm& n, int H)
 bool use_sweep(const sm_ctx* ctx, const Norm& n, int H)
 {
     if (ctx->dbg_flags & (DBG_LEGACY | DBG_ROW)) return false;
+    if (deep(n)) return false;  // no sweep instance above kSweepMaxD
     // every configuration whose preconditions hold: with wide strips (sm_sweep.hpp SweepGeo)
     // census 8 paths run 217 vs 249 us per KITTI pair against the per-direction engine, u16
     // costs at 8 paths (OpenCV MODE_HH, mc-cnn volumes) 1.5-1.7x faster
@@ -1349,7 +1424,9 @@ int launch_cost2_s(sm_ctx* ctx, const Norm& n, const Geo& g, const smk::SgbmCost
     const int want = std::max(1, wgs / std::max(1, strips * g.G));
     c2.band = std::max({(sc.Yc + want - 1) / want, 8, 4 * S});
     const int bands = (sc.Yc + c2.band - 1) / c2.band;
-    if (one)
+    if (deep(n))  // (rpairs > bd there: the four-slot form) stores through per-row descriptors
+        hipLaunchKernelGGL((smk::k_sgbm_cost2<S, CPT, -4>), dim3(strips, bands, g.G), dim3(bd), lds, ctx->stream, c2);
+    else if (one)
         hipLaunchKernelGGL((smk::k_sgbm_cost2<S, CPT, 1>), dim3(strips, bands, g.G), dim3(bd), lds, ctx->stream, c2);
     else
         hipLaunchKernelGGL((smk::k_sgbm_cost2<S, CPT, 4>), dim3(strips, bands, g.G), dim3(bd), lds, ctx->stream, c2);
@@ -1660,6 +1737,24 @@ int run_group(sm_ctx* ctx, const Src& src, const Geo& g, const Norm& n, int16_t*
                                    dim3(256),
                                    0, ctx->stream, c8);
                 HIP_TRY(ctx, hipGetLastError());
+            } else if (deep(n)) {
+                // the same u8 volume from the plain kernel (k_census_cost8 stages 64 + 255 right
+                // codes and 16 chunks per column: D <= 256), one launch per pair
+                if ((rc = ensure(ctx, bs.cost, (size_t)G * g.vol)) != SM_OK) return rc;
+                for (int i = 0; i < G; i++) {
+                    smk::CensusCostArgs cc{};
+                    cc.cl = ca.out[0] + (size_t)i * g.census_pair;
+                    cc.cr = ca.out[1] + (size_t)i * g.census_pair;
+                    cc.C = (uint8_t*)bs.cost.p + (size_t)i * g.vol;
+                    cc.H = H;
+                    cc.W = W;
+                    cc.width1 = n.width1;
+                    cc.D = n.D;
+                    cc.minD = n.minD;
+                    cc.minX1 = n.minX1;
+                    hipLaunchKernelGGL(smk::k_census_cost, dim3(grid_for(g.vol / 8)), dim3(256), 0, ctx->stream, cc);
+                }
+                HIP_TRY(ctx, hipGetLastError());
             }
         } else if (n.cost == SM_COST_VOLUME) {
             if ((rc = ensure(ctx, bs.cost, (size_t)G * g.vol * 2)) != SM_OK) return rc;
@@ -1704,9 +1799,14 @@ int run_group(sm_ctx* ctx, const Src& src, const Geo& g, const Norm& n, int16_t*
             va.scale = src.scale;
             va.nt = cost_nt(g, 2);
             va.zero_word = gflag;
-            // 64-column tiles measured faster than 128 (117 vs 130 us/pair at D=192)
-            hipLaunchKernelGGL(smk::k_cost_volume_f32<64>, dim3((n.width1 + 63) / 64, H, G), dim3(256),
-                               (size_t)64 * (n.D / 2 + 1) * 4, ctx->stream, va);
+            // 64-column tiles measured faster than 128 (117 vs 130 us/pair at D=192); D > 256: 32
+            // columns (64 need more LDS than a workgroup has at D = 512)
+            if (deep(n))
+                hipLaunchKernelGGL(smk::k_cost_volume_f32_deep, dim3((n.width1 + 31) / 32, H, G), dim3(256),
+                                   (size_t)32 * (n.D / 2 + 1) * 4, ctx->stream, va);
+            else
+                hipLaunchKernelGGL(smk::k_cost_volume_f32<64>, dim3((n.width1 + 63) / 64, H, G), dim3(256),
+                                   (size_t)64 * (n.D / 2 + 1) * 4, ctx->stream, va);
             HIP_TRY(ctx, hipGetLastError());
         } else {
             if ((rc = ensure(ctx, ctx->planes, (size_t)G * 2 * H * W * 8)) != SM_OK) return rc;

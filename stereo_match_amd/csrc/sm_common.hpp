@@ -11,14 +11,17 @@ namespace smk {
 // loop (x86 builds): each int16 lane (d mod 8) keeps its first minimum and the lowest
 // lane holding the overall minimum wins, so equal minima rank by (d mod 8, d)
 // (oracle/sgm_np.py:wta_best).  MODE_HH (8 paths) keeps the first minimum.  The rank
-// sits in the low 16 bits of the (S << 16 | rank) min-keys; D <= 256.
+// sits in the low 16 bits of the (S << 16 | rank) min-keys; RB = bits of d >> 3: 5 serve
+// D <= 256, 6 D <= 512 (the same order of equal minima).
+template <int RB = 5>
 __device__ __forceinline__ uint32_t wta_rank(int d, bool lane8)
 {
-    return lane8 ? ((((uint32_t)d & 7u) << 5) | ((uint32_t)d >> 3)) : (uint32_t)d;
+    return lane8 ? ((((uint32_t)d & 7u) << RB) | ((uint32_t)d >> 3)) : (uint32_t)d;
 }
+template <int RB = 5>
 __device__ __forceinline__ int wta_unrank(uint32_t r, bool lane8)
 {
-    return lane8 ? (int)(((r & 31u) << 3) | (r >> 5)) : (int)r;
+    return lane8 ? (int)(((r & ((1u << RB) - 1u)) << 3) | (r >> RB)) : (int)r;
 }
 
 constexpr int kMaxDirs = 8;

@@ -506,9 +506,14 @@ struct SgbmCost2Args {
     int nt;  // 1: nontemporal stores (the launch group's volume exceeds the Infinity Cache)
 };
 
+// NLR: prefetch slots per thread.  Negative (numDisparities > 256: -NLR slots, ROWS): the output
+// descriptor covers the one row a step writes, from a 64-bit row base, so the 32-bit store
+// offsets stay inside a row whatever the volume's size (2880 x 1988 at D = 512: 4.8 GB).  (One
+// template: a shared body behind two kernels changed the registers of the NLR > 0 instances.)
 template <int S, int CPT, int NLR>
 __global__ void __launch_bounds__(256) k_sgbm_cost2(SgbmCost2Args a)
 {
+    constexpr bool ROWS = NLR < 0;
     constexpr int R = 2 * S + 1;
     extern __shared__ __attribute__((aligned(16))) uint32_t dsm[];
     const int D = a.D, NP = D >> 1, CG = blockDim.x / NP, TX = CG * CPT, NHC = TX + 2 * S;
@@ -537,7 +542,7 @@ __global__ void __launch_bounds__(256) k_sgbm_cost2(SgbmCost2Args a)
     const int r0 = yb0 - S, nsteps = yb1 + S - r0;  // input rows r0 .. yb1-1+S
 
     // register prefetch of one input row's planes: left halo columns, right column pairs
-    constexpr int NL = NLR, NR = NLR;  // host: NHC, rpairs <= NLR * blockDim
+    constexpr int NL = ROWS ? -NLR : NLR, NR = NL;  // host: NHC, rpairs <= NL * blockDim
     uint2 pl[NL], pr0[NR], pr1[NR];
     auto load_row = [&](int r) {
         const int y = min(max(r, 0), a.H - 1);
@@ -686,7 +691,15 @@ __global__ void __launch_bounds__(256) k_sgbm_cost2(SgbmCost2Args a)
 #pragma unroll
                 for (int j = 0; j < 2 * S + 1; j++) h += v[j];
                 const int y = r0 + st - S;  // output row of this step (valid when st >= 2S)
-                const uint32_t ob = (((uint32_t)max(y, 0) * W1 + x0 + hx0) * D + 2 * p) * 2;
+                uint32_t ob;
+                rsrc_t ro;
+                if constexpr (ROWS) {
+                    ob = (((uint32_t)(x0 + hx0)) * D + 2 * p) * 2;
+                    ro = make_rsrc(a.C + pair * a.C_pair + (size_t)max(y, 0) * W1 * D, (uint64_t)W1 * D * 2);
+                } else {
+                    ob = (((uint32_t)max(y, 0) * W1 + x0 + hx0) * D + 2 * p) * 2;
+                    ro = rc;
+                }
                 const int nval = st >= 2 * S ? W1 - (x0 + hx0) : 0;
 #pragma unroll
                 for (int i = 0; i < CPT; i++) {
@@ -695,8 +708,8 @@ __global__ void __launch_bounds__(256) k_sgbm_cost2(SgbmCost2Args a)
                     ring[q][i] = h;
                     // column step as the scalar offset: one voffset for all CPT stores
                     if (i < nval) {
-                        if (a.nt) __builtin_amdgcn_raw_buffer_store_b32(vs[i], rc, ob, i * 2 * D, 2);
-                        else __builtin_amdgcn_raw_buffer_store_b32(vs[i], rc, ob, i * 2 * D, 0);
+                        if (a.nt) __builtin_amdgcn_raw_buffer_store_b32(vs[i], ro, ob, i * 2 * D, 2);
+                        else __builtin_amdgcn_raw_buffer_store_b32(vs[i], ro, ob, i * 2 * D, 0);
                     }
                     vs[i] -= ring[(q + 1) % R][i];  // row r - 2S leaves the window
                 }
@@ -922,6 +935,48 @@ __global__ void __launch_bounds__(256) k_cost_volume_f32(VolArgs a)
             if (in1) q1 = x_in ? quant_cost_n(c1[k], qoff, qsc, nclamp, nnan) : quant_cost(c1[k], qoff, qsc);
             tile[(xl + k) * rowdw + dp] = q0 | (q1 << 16);
         }
+    }
+    if (a.clamped) {  // one atomic per wave that saw any
+        nclamp = group_sum_u32_wave(nclamp);
+        nnan = group_sum_u32_wave(nnan);
+        if ((threadIdx.x & 63) == 0) {
+            if (nclamp) atomicAdd(a.clamped, (unsigned long long)nclamp);
+            if (nnan) atomicAdd(a.nans, (unsigned long long)nnan);
+        }
+    }
+    __syncthreads();
+    uint32_t* out = reinterpret_cast<uint32_t*>(a.C + pair * a.C_pair + ((size_t)y * a.width1 + x0) * a.D);
+    const int total = nx * half;
+    for (int i = threadIdx.x; i < total; i += 256) {
+        const int xl = i / half, j = i - xl * half;
+        if (a.nt) __builtin_nontemporal_store(tile[xl * rowdw + j], out + i);
+        else out[i] = tile[xl * rowdw + j];
+    }
+}
+
+// numDisparities > 256: 32-column tiles, [32][D/2 + 1] words of LDS (64 columns at D = 512 are
+// 65792 B, past a workgroup's 64 KiB); a half-wave reads 32 consecutive floats of a plane row.
+// Same quantisation, pad planes and counters as k_cost_volume_f32.
+__global__ void __launch_bounds__(256) k_cost_volume_f32_deep(VolArgs a)
+{
+    clear_group_flag(a.zero_word);
+    constexpr int TX = 32;
+    extern __shared__ uint32_t tile[];
+    const int half = a.D >> 1, rowdw = half + 1;
+    const int x0 = blockIdx.x * TX, y = blockIdx.y, pair = blockIdx.z;
+    const float qoff = a.win ? a.win[2 * pair] : a.offset, qsc = a.win ? a.win[2 * pair + 1] : a.scale;
+    uint32_t nclamp = 0, nnan = 0;
+    const int nx = min(TX, a.width1 - x0);
+    const size_t plane = (size_t)a.H * a.W;
+    const float* v = a.vol + pair * a.vol_pair + (size_t)y * a.W + a.minX1 + x0;
+    for (int i = threadIdx.x; i < TX * half; i += 256) {
+        const int xl = i & (TX - 1), dp = i >> 5;
+        if (xl >= nx) continue;  // (columns past the domain are never stored)
+        const float* p0 = v + (size_t)(2 * dp) * plane + xl;
+        uint32_t q0 = (uint32_t)a.cpad, q1 = (uint32_t)a.cpad;
+        if (2 * dp < a.Dv) q0 = quant_cost_n(__builtin_nontemporal_load(p0), qoff, qsc, nclamp, nnan);
+        if (2 * dp + 1 < a.Dv) q1 = quant_cost_n(__builtin_nontemporal_load(p0 + plane), qoff, qsc, nclamp, nnan);
+        tile[xl * rowdw + dp] = q0 | (q1 << 16);
     }
     if (a.clamped) {  // one atomic per wave that saw any
         nclamp = group_sum_u32_wave(nclamp);

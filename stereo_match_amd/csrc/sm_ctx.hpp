@@ -1,7 +1,7 @@
 // sm_ctx.hpp — the host-side context of the C-ABI, shared by its translation units
 // (sm_api.hip: the matcher core; sm_api_image.hip, sm_api_cloud.hip, sm_api_png.hip,
 // sm_api_jpeg.hip, sm_api_mccnn.hip: the leaf subsystems).  Host code only: every kernel header is compiled
-// in exactly one unit, so none is included here.  fail, ensure, get_event, stage_in,
+// in exactly one unit (sm_paths.hpp, all templates, also in sm_deep.hip's), so none is included here.  fail, ensure, get_event, stage_in,
 // stage_out and check_sweep_errors are defined once, in sm_api.hip.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -665,6 +665,7 @@ __device__ __forceinline__ void wta_row(const WtaArgs& a, const int y, const int
     const LT* __restrict__ Lb = (const LT*)(a.L + (size_t)pair * a.L_pair_bytes) + g * DPL;
     const size_t slot = a.slot_bytes / sizeof(LT);
     const int u = a.uniq;
+    constexpr int RB = DPL > 16 ? 6 : 5;  // wta_rank: bits of d >> 3 (D > 256: sm_deep.hip's instances)
     if constexpr (DPL % 2 == 0) {
         // the in-sweep lines' patched partial (PART_ONLY), or u16 direction volumes (+ partial)
         if constexpr (PART_ONLY) {
@@ -746,10 +747,10 @@ __device__ __forceinline__ void wta_row(const WtaArgs& a, const int y, const int
         for (int i = 0; i < DPL; i++) {
             S[i] = min(S[i], 32767u);
             if (g * DPL + i >= a.Dv) S[i] = 0xFFFFu;  // pad planes of a cost volume: never the minimum
-            key = min(key, (S[i] << 16) | wta_rank(g * DPL + i, a.lane8));
+            key = min(key, (S[i] << 16) | wta_rank<RB>(g * DPL + i, a.lane8));
         }
         key = row16_min(key);
-        const int minS = (int)(key >> 16), best = wta_unrank(key & 0xFFFF, a.lane8);
+        const int minS = (int)(key >> 16), best = wta_unrank<RB>(key & 0xFFFF, a.lane8);
         uint32_t bad = 0, nb = 0;
 #pragma unroll
         for (int i = 0; i < DPL; i++) {
