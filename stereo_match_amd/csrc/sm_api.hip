@@ -2300,6 +2300,9 @@ int normalize_bm(sm_ctx* ctx, const sm_bm_params* p, int H, int W, BmNorm& n)
     return SM_OK;
 }
 
+constexpr size_t kBmValidateLdsPerColumn = 8 + 4 + 1;  // key2, d2v, kill of k_bm_validate
+constexpr size_t kBmValidateMaxLds = 163840;            // gfx950: LDS one workgroup may declare
+
 int run_bm(sm_ctx* ctx, const uint8_t* dL, const uint8_t* dR, size_t pair_stride, int npairs, int H, int W,
            int stride, const BmNorm& n, int16_t* d_out)
 {
@@ -2320,7 +2323,16 @@ int run_bm(sm_ctx* ctx, const uint8_t* dL, const uint8_t* dR, size_t pair_stride
             break;
         }
     }
-    if (region && !sws) return fail(ctx, SM_E_UNSUPPORTED, "blockSize/numDisparities too large for the GPU BM kernel");
+    if (region && !sws)
+        return fail(ctx, SM_E_UNSUPPORTED,
+                    "blockSize %d with numDisparities %d is too large for the GPU BM kernel (64 KiB of LDS per strip)",
+                    2 * n.SW2 + 1, n.ndisp);
+    // k_bm_validate keeps one row in LDS: a key, a disparity and a flag per column
+    const size_t vlds = (size_t)W * kBmValidateLdsPerColumn;
+    if (region && n.d12 >= 0 && vlds > kBmValidateMaxLds)
+        return fail(ctx, SM_E_UNSUPPORTED,
+                    "width %d with disp12MaxDiff >= 0: validateDisparity holds a row in LDS, %d columns at the most", W,
+                    (int)(kBmValidateMaxLds / kBmValidateLdsPerColumn));
     const int G = std::min(npairs, kMaxGroup);
     int rc;
     for (int i = 0; i < 2; i++)
@@ -2382,7 +2394,10 @@ int run_bm(sm_ctx* ctx, const uint8_t* dL, const uint8_t* dR, size_t pair_stride
                 va.minD = n.minD;
                 va.ndisp = n.ndisp;
                 va.maxdiff16 = n.d12 * 16;
-                hipLaunchKernelGGL(smk::k_bm_validate, dim3(H, g), dim3(256), (size_t)W * 13, ctx->stream, va);
+                if (vlds > 48 * 1024)  // above the default limit of dynamic LDS
+                    HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(smk::k_bm_validate),
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)vlds));
+                hipLaunchKernelGGL(smk::k_bm_validate, dim3(H, g), dim3(256), vlds, ctx->stream, va);
                 HIP_TRY(ctx, hipGetLastError());
             }
         }

@@ -56,6 +56,22 @@ def test_bm_full_size_kitti(eng, D, bs):
     assert np.array_equal(eng.bm_compute(right, left, bm_params(rp)), bm_np.stereo_bm(right, left, rp))
 
 
+@pytest.mark.parametrize("D,bs", [(128, 21), (256, 41)])
+def test_bm_full_size_kitti_every_pixel(eng, D, bs):
+    """The same frames with textureThreshold = uniquenessRatio = 0: with the defaults the oracle
+    filters 70 % (D 128) and 83 % (D 256) of the ROI, here it keeps every pixel of it, so the WTA
+    and the sub-pixel fit at strip widths 32 and 8 are compared everywhere.  (The right matcher
+    of test_bm_full_size_kitti runs with these thresholds already.)"""
+    H, W, _ = synthetic.CONFIGS["kitti"]
+    left, right, gt = synthetic.random_dot_pair(H, W, D, seed=12)
+    p = dict(numDisparities=D, blockSize=bs, textureThreshold=0, uniquenessRatio=0)
+    exp = bm_np.stereo_bm(left, right, p)
+    x, y, w, h = bm_np.valid_roi(H, W, bm_np.normalize_bm(p))
+    assert (exp[y:y + h, x:x + w] != -16).all()
+    out = eng.bm_compute(left, right, bm_params(p))
+    assert np.array_equal(out, exp), f"{np.sum(out != exp)} px differ"
+
+
 def test_compute_disparity_bm_end_to_end():
     """method="BM": left BM (WLS-mutated), right BM, WLS with BM offsets."""
     import stereo_match_amd as sm
