@@ -849,6 +849,60 @@ int sm_mccnn_features_host(int L, const float* const* w, const float* const* b, 
 int sm_mccnn_join_host(const float* feat_a, const float* feat_b, int n, int H, int W, int D, int min_disparity,
                        float* vol);
 
+/* ---- MC-CNN's stereo method after the matching cost: the paper's semi-global
+ * matching on the float32 volume, left-right interpolation, sub-pixel step, 5x5 median and
+ * bilateral filter.  Section 4 of the paper restated; parity with mc-cnn's code is unpinned.
+ * The device and the *_host functions (plain C++, no context, no device) give the same values.
+ *
+ * Volumes: float32 [n][D][H][W], D in 1..256, NaN where a cell does not exist: what
+ * sm_mccnn_volume[_device] writes for (a, b, D, min_disparity).  a is the view's own uint8 gray
+ * image and b the other one (n of them image_stride bytes apart, rows row_stride bytes apart);
+ * both go through the grey-level table of 4.15, and a constant image counts as all zeros.  The
+ * right view is the same call with the images swapped and min_disparity = -(min_disparity + D) + 1.
+ *
+ * sm_mcsgm_aggregate*: four paths (from the left, right, above, below), averaged; sgm_i repeats
+ * the step on its own result.  W <= 4096.  The output may not overlap the input (SM_E_ARG).
+ * pi1 and pi2 may be 0; sgm_q1, sgm_q2, sgm_v, sgm_d must be positive and finite, sgm_i 1..16.
+ *
+ * sm_mcsgm_disparity*: the left view's disparity map float32 [n][H][W] from the two aggregated
+ * volumes (agg_r that of the right view) and the left image; an invalid pixel is
+ * float(min_disparity - 1).  |min_disparity| and |min_disparity + D| <= 2^23; blur_sigma and
+ * blur_t positive, ceil(3 blur_sigma) <= 48.  stages (may be NULL, and so may each member)
+ * receives the maps in between, [n][H][W] each: the integer disparities of both views after
+ * winner-take-all (invalid: min_disparity - 1), the status of the left pixels (0 correct,
+ * 1 mismatch, 2 occluded), the interpolated map, and the maps after the sub-pixel step and the
+ * median.  The device entry points run on the context's stream and wait once for the images'
+ * sums; scratch belongs to the context. */
+typedef struct sm_mcsgm_params {
+    float pi1, pi2, sgm_q1, sgm_q2, sgm_v, sgm_d;
+    int sgm_i;
+    float blur_sigma, blur_t;
+} sm_mcsgm_params;
+typedef struct sm_mcsgm_stages {
+    int32_t *wta_left, *wta_right, *status, *filled;
+    float *subpixel, *median;
+} sm_mcsgm_stages;
+/* The paper's KITTI fast values as recalled (unverified): 4, 55.72, 3, 2.5, 1.5, 0.02, 1, 7.74, 5. */
+int sm_mcsgm_default_params(sm_mcsgm_params* out);
+int sm_mcsgm_aggregate_device(sm_ctx* ctx, const float* d_vol, const uint8_t* d_a, const uint8_t* d_b, int n,
+                              size_t image_stride, int H, int W, size_t row_stride, int D, int min_disparity,
+                              const sm_mcsgm_params* params, float* d_agg);
+int sm_mcsgm_disparity_device(sm_ctx* ctx, const float* d_agg_l, const float* d_agg_r, const uint8_t* d_a, int n,
+                              size_t image_stride, int H, int W, size_t row_stride, int D, int min_disparity,
+                              const sm_mcsgm_params* params, float* d_disp, const sm_mcsgm_stages* d_stages);
+/* Host pointers in and out (images packed: rows W bytes, images H * W bytes apart). */
+int sm_mcsgm_aggregate(sm_ctx* ctx, const float* vol, const uint8_t* a, const uint8_t* b, int n, int H, int W, int D,
+                       int min_disparity, const sm_mcsgm_params* params, float* agg);
+int sm_mcsgm_disparity(sm_ctx* ctx, const float* agg_l, const float* agg_r, const uint8_t* a, int n, int H, int W, int D,
+                       int min_disparity, const sm_mcsgm_params* params, float* disp, const sm_mcsgm_stages* stages);
+/* The CPU twin of the two steps. */
+int sm_mcsgm_aggregate_host(const float* vol, const uint8_t* a, const uint8_t* b, int n, size_t image_stride, int H,
+                            int W, size_t row_stride, int D, int min_disparity, const sm_mcsgm_params* params,
+                            float* agg);
+int sm_mcsgm_disparity_host(const float* agg_l, const float* agg_r, const uint8_t* a, int n, size_t image_stride, int H,
+                            int W, size_t row_stride, int D, int min_disparity, const sm_mcsgm_params* params,
+                            float* disp, const sm_mcsgm_stages* stages);
+
 /* Last error text of ctx (or of the calling thread when ctx == NULL). */
 const char* sm_last_error(sm_ctx* ctx);
 

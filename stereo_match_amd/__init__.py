@@ -24,6 +24,9 @@ Public surface (mirrors the reference / OpenCV names the reference uses):
   ``disparity_test.py:79-80``, ``mapTo3D.py:78-79``), decoded on the device
 * :class:`McCnnFast` — the mc-cnn *fast* matching cost, images to the float32 cost volume of
   :meth:`StereoSGBM.computeFromCost` (``mc_cnn/script.py:9``, ``mapTo3D_mc_cnn.py:71``)
+* :class:`McCnnStereo`, :func:`mc_aggregate`, :func:`mc_disparity`, :class:`McCnnStereoParams` — mc-cnn's
+  own stereo method on that volume: its SGM, left-right interpolation, sub-pixel step, median and
+  bilateral filter, up to the disparity maps ``mapTo3D_mc_cnn.py:70-77`` reads
 
 All compute runs in ``libstereo_match_amd.so`` (HIP, gfx950) through the
 C-ABI in ``include/stereo_match_amd.h``; there is no CPU fallback.
@@ -45,6 +48,8 @@ from . import filters
 from .filters import gaussian_filter, image_measure, pyrDown
 from . import mccnn
 from .mccnn import McCnnFast
+from . import mcstereo
+from .mcstereo import McCnnStereo, McCnnStereoParams, mc_aggregate, mc_disparity
 
 __all__ = [
     "compute_disparity", "matcher_from_settings", "StereoSGBM", "StereoSGBM_create", "createRightMatcher",
@@ -59,5 +64,6 @@ __all__ = [
     "decode_disparity_png",
     "filters", "gaussian_filter", "image_measure", "pyrDown",
     "mccnn", "McCnnFast",
+    "mcstereo", "McCnnStereo", "McCnnStereoParams", "mc_aggregate", "mc_disparity",
 ]
 __version__ = "0.1.0"

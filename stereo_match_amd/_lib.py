@@ -97,6 +97,20 @@ class SmJpegDecParams(ctypes.Structure):
                 ("subsampling", ctypes.c_int), ("max_file_bytes", ctypes.c_uint64), ("d_desc", ctypes.c_void_p)]
 
 
+class SmMcsgmParams(ctypes.Structure):
+    """Mirror of ``struct sm_mcsgm_params`` (MC-CNN's stereo method: SGM penalties, bilateral filter)."""
+    _fields_ = [(n, ctypes.c_float) for n in ("pi1", "pi2", "sgm_q1", "sgm_q2", "sgm_v", "sgm_d")] + [
+        ("sgm_i", ctypes.c_int), ("blur_sigma", ctypes.c_float), ("blur_t", ctypes.c_float)]
+
+
+class SmMcsgmStages(ctypes.Structure):
+    """Mirror of ``struct sm_mcsgm_stages``: where the maps between the steps go (0: not wanted)."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("wta_left", "wta_right", "status", "filled", "subpixel", "median")]
+
+
+MCSGM_STAGES = tuple(n for n, _ in SmMcsgmStages._fields_)
+MCSGM_INT_STAGES = MCSGM_STAGES[:4]  # int32 maps; the other two are float32
+
 SM_PNG_SEG = 32768
 SM_PNGDEC_CAP = 32768
 SM_PNGDEC_U8, SM_PNGDEC_U16, SM_PNGDEC_DISP_I16, SM_PNGDEC_DISP_F32 = 0, 1, 2, 3
@@ -249,6 +263,24 @@ _SIGS = {
                                           _c.c_int, _c.c_size_t, _c.c_int, _c.c_int, _c.c_size_t, _c.c_void_p]),
     "sm_mccnn_join_host": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
                                       _c.c_void_p]),
+    "sm_mcsgm_default_params": (_c.c_int, [_c.POINTER(SmMcsgmParams)]),
+    "sm_mcsgm_aggregate_device": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_size_t,
+                                             _c.c_int, _c.c_int, _c.c_size_t, _c.c_int, _c.c_int,
+                                             _c.POINTER(SmMcsgmParams), _c.c_void_p]),
+    "sm_mcsgm_disparity_device": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_size_t,
+                                             _c.c_int, _c.c_int, _c.c_size_t, _c.c_int, _c.c_int,
+                                             _c.POINTER(SmMcsgmParams), _c.c_void_p, _c.POINTER(SmMcsgmStages)]),
+    "sm_mcsgm_aggregate": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int,
+                                      _c.c_int, _c.c_int, _c.POINTER(SmMcsgmParams), _c.c_void_p]),
+    "sm_mcsgm_disparity": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int,
+                                      _c.c_int, _c.c_int, _c.POINTER(SmMcsgmParams), _c.c_void_p,
+                                      _c.POINTER(SmMcsgmStages)]),
+    "sm_mcsgm_aggregate_host": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_size_t, _c.c_int,
+                                           _c.c_int, _c.c_size_t, _c.c_int, _c.c_int, _c.POINTER(SmMcsgmParams),
+                                           _c.c_void_p]),
+    "sm_mcsgm_disparity_host": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_size_t, _c.c_int,
+                                           _c.c_int, _c.c_size_t, _c.c_int, _c.c_int, _c.POINTER(SmMcsgmParams),
+                                           _c.c_void_p, _c.POINTER(SmMcsgmStages)]),
     "sm_bm_default_params": (_c.c_int, [_c.c_int, _c.c_int, _c.POINTER(SmBmParams)]),
     "sm_bm_right_matcher_params": (_c.c_int, [_c.POINTER(SmBmParams), _c.POINTER(SmBmParams)]),
     "sm_bm_compute": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int,
@@ -446,6 +478,39 @@ def mccnn_join_host(fa: np.ndarray, fb: np.ndarray, D: int, min_disparity: int) 
     if rc != SM_OK:
         _raise(rc, None)
     return vol
+
+
+def mcsgm_stage_arrays(n: int, H: int, W: int):
+    """Empty numpy maps for every member of ``sm_mcsgm_stages`` and the struct that points at them."""
+    maps = {k: np.empty((n, H, W), np.int32 if k in MCSGM_INT_STAGES else np.float32) for k in MCSGM_STAGES}
+    return maps, SmMcsgmStages(*[maps[k].ctypes.data for k in MCSGM_STAGES])
+
+
+def mcsgm_aggregate_host(vol: np.ndarray, a: np.ndarray, b: np.ndarray, image_stride: int, row_stride: int,
+                         min_disparity: int, prm: "SmMcsgmParams") -> np.ndarray:
+    """sm_mcsgm_aggregate_host: the CPU twin's aggregated volume of ``vol`` [n, D, H, W] (float32,
+    contiguous) and the n images inside ``a`` / ``b`` (uint8; one geometry for both)."""
+    n, D, H, W = vol.shape
+    agg = np.empty_like(vol)
+    rc = load().sm_mcsgm_aggregate_host(vol.ctypes.data, a.ctypes.data, b.ctypes.data, n, image_stride, H, W, row_stride,
+                                        D, min_disparity, ctypes.byref(prm), agg.ctypes.data)
+    if rc != SM_OK:
+        _raise(rc, None)
+    return agg
+
+
+def mcsgm_disparity_host(agg_l: np.ndarray, agg_r: np.ndarray, a: np.ndarray, image_stride: int, row_stride: int,
+                         min_disparity: int, prm: "SmMcsgmParams", stages: bool):
+    """sm_mcsgm_disparity_host: (disparity [n, H, W] float32, dict of the stage maps or None)."""
+    n, D, H, W = agg_l.shape
+    disp = np.empty((n, H, W), np.float32)
+    maps, st = mcsgm_stage_arrays(n, H, W) if stages else (None, None)
+    rc = load().sm_mcsgm_disparity_host(agg_l.ctypes.data, agg_r.ctypes.data, a.ctypes.data, n, image_stride, H, W,
+                                        row_stride, D, min_disparity, ctypes.byref(prm), disp.ctypes.data,
+                                        ctypes.byref(st) if stages else None)
+    if rc != SM_OK:
+        _raise(rc, None)
+    return disp, maps
 
 
 def volume_scale(scale) -> float:
@@ -919,6 +984,38 @@ class Engine:
                             D: int, min_disparity: int, d_vol: int):
         self._check(self._lib.sm_mccnn_volume_device(self.ctx, d_a, d_b, n, image_stride, H, W, row_stride, D,
                                                      min_disparity, d_vol))
+
+    def mcsgm_aggregate(self, vol: np.ndarray, a: np.ndarray, b: np.ndarray, min_disparity: int,
+                        prm: "SmMcsgmParams") -> np.ndarray:
+        """sm_mcsgm_aggregate: contiguous float32 [n, D, H, W] and uint8 [n, H, W] images."""
+        n, D, H, W = vol.shape
+        agg = np.empty_like(vol)
+        self._check(self._lib.sm_mcsgm_aggregate(self.ctx, vol.ctypes.data, a.ctypes.data, b.ctypes.data, n, H, W, D,
+                                                 min_disparity, ctypes.byref(prm), agg.ctypes.data))
+        return agg
+
+    def mcsgm_disparity(self, agg_l: np.ndarray, agg_r: np.ndarray, a: np.ndarray, min_disparity: int,
+                        prm: "SmMcsgmParams", stages: bool):
+        """sm_mcsgm_disparity: (disparity [n, H, W] float32, dict of the stage maps or None)."""
+        n, D, H, W = agg_l.shape
+        disp = np.empty((n, H, W), np.float32)
+        maps, st = mcsgm_stage_arrays(n, H, W) if stages else (None, None)
+        self._check(self._lib.sm_mcsgm_disparity(self.ctx, agg_l.ctypes.data, agg_r.ctypes.data, a.ctypes.data, n, H, W, D,
+                                                 min_disparity, ctypes.byref(prm), disp.ctypes.data,
+                                                 ctypes.byref(st) if stages else None))
+        return disp, maps
+
+    def mcsgm_aggregate_device(self, d_vol: int, d_a: int, d_b: int, n: int, image_stride: int, H: int, W: int,
+                               row_stride: int, D: int, min_disparity: int, prm: "SmMcsgmParams", d_agg: int):
+        self._check(self._lib.sm_mcsgm_aggregate_device(self.ctx, d_vol, d_a, d_b, n, image_stride, H, W, row_stride, D,
+                                                        min_disparity, ctypes.byref(prm), d_agg))
+
+    def mcsgm_disparity_device(self, d_agg_l: int, d_agg_r: int, d_a: int, n: int, image_stride: int, H: int, W: int,
+                               row_stride: int, D: int, min_disparity: int, prm: "SmMcsgmParams", d_disp: int,
+                               stages: "SmMcsgmStages" = None):
+        self._check(self._lib.sm_mcsgm_disparity_device(self.ctx, d_agg_l, d_agg_r, d_a, n, image_stride, H, W, row_stride,
+                                                        D, min_disparity, ctypes.byref(prm), d_disp,
+                                                        ctypes.byref(stages) if stages is not None else None))
 
     def nlm_denoise(self, src: np.ndarray, h: float, template_window: int, search_window: int,
                     dst: np.ndarray = None) -> np.ndarray:

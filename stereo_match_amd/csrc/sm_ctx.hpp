@@ -1,6 +1,6 @@
 // sm_ctx.hpp — the host-side context of the C-ABI, shared by its translation units
 // (sm_api.hip: the matcher core; sm_api_image.hip, sm_api_cloud.hip, sm_api_png.hip,
-// sm_api_jpeg.hip, sm_api_mccnn.hip: the leaf subsystems).  Host code only: every kernel header is compiled
+// sm_api_jpeg.hip, sm_api_mccnn.hip, sm_api_mcsgm.hip: the leaf subsystems).  Host code only: every kernel header is compiled
 // in exactly one unit (sm_paths.hpp, all templates, also in sm_deep.hip's), so none is included here.  fail, ensure, get_event, stage_in,
 // stage_out and check_sweep_errors are defined once, in sm_api.hip.
 #pragma once
@@ -91,6 +91,19 @@ struct sm_ctx {
         std::vector<float> tab_host;
         int L = 0;
     } mccnn;
+    // MC-CNN's stereo method (sm_mcsgm.hpp): the images' sums and grey-level tables (and their host
+    // copies, which outlive the transfers), the normalised images, the vertical paths, the volume
+    // between two iterations, the bilateral weights (cached for sigma_bits); the stage maps a
+    // caller did not ask for; volumes, images and results of the host-pointer calls
+    struct {
+        DevBuf sums, tab, ta, tb, l2, l3, iter, w;
+        DevBuf wta_l, wta_r, status, filled, sub, med;
+        DevBuf in_vol, in_vol_r, in_a, in_b, out;
+        std::vector<unsigned long long> sums_host;
+        std::vector<float> tab_host, w_host;
+        uint32_t sigma_bits = 0;
+        int R = -1;
+    } mcsgm;
     struct { DevBuf a; } filter;  // image_measure: the first Gaussian's result, [img][H][W] float64
     DevBuf wls_num, wls_den, wls_inter, wls_w, wls_disp[2], wls_out;  // WLS scratch
     DevBuf wls_R, wls_IT;         // WLS: Thomas pivots / elimination factors of every pass

@@ -225,7 +225,7 @@ inline void mccnn_join_host(const float* fa, const float* fb, int n, int H, int 
     }
 }
 
-#if defined(__HIPCC__)
+#if defined(__HIPCC__) && !defined(SM_MCCNN_NO_KERNELS)  // sm_mcsgm.hpp's unit takes the host functions only
 // ---- kernels
 
 constexpr int MC_BLOCK = 256;
@@ -490,6 +490,6 @@ __global__ __launch_bounds__(MC_JX) void k_mc_join(McJoinArgs a)
         }
     }
 }
-#endif  // __HIPCC__
+#endif  // __HIPCC__ && !SM_MCCNN_NO_KERNELS
 
 }  // namespace smk
