@@ -903,6 +903,49 @@ int sm_mcsgm_disparity_host(const float* agg_l, const float* agg_r, const uint8_
                             int W, size_t row_stride, int D, int min_disparity, const sm_mcsgm_params* params,
                             float* disp, const sm_mcsgm_stages* stages);
 
+/* ---- Cross-based cost aggregation of MC-CNN's stereo method: the matching cost
+ * averaged over a support region that follows the edges of both images (section 4.1 of the paper
+ * restated; parity with mc-cnn's code is unpinned).  The device and the *_host functions (plain
+ * C++, no context, no device) give the same values.
+ *
+ * Images, volumes, a / b and min_disparity are those of sm_mcsgm_aggregate*; W <= 4096.
+ *
+ * sm_mccbca_arms*: uint8 [n][4][H][W], the arms of every pixel to the left, right, up and down:
+ * the largest k <= l1 - 1 such that every pixel up to k steps away is inside the image and differs
+ * from the pixel by less than tau1 (through the grey-level table of 4.15; a constant image counts
+ * as all zeros).
+ *
+ * sm_mccbca_aggregate*: `iterations` (1..16) steps.  One step leaves a cell whose column of b is
+ * outside the image as it is; every other cell becomes the sum of the costs over its region
+ * divided by the region's size, where the region's arms are the shorter of a's at x and b's at
+ * x - (min_disparity + d): first along the rows, then the row sums down the columns, float32 adds
+ * in ascending order.  The output may not overlap the input (SM_E_ARG).  l1 1..32, tau1 finite and
+ * positive, i1 and i2 0..16 (the iterations before and after the semi-global matching; these
+ * functions validate them and use `iterations`).  The device entry points run on the context's
+ * stream and wait once for the images' sums; scratch belongs to the context. */
+typedef struct sm_mccbca_params {
+    int l1;
+    float tau1;
+    int i1, i2;
+} sm_mccbca_params;
+/* The paper's KITTI accurate values as recalled (unverified): 5, 0.13, 2, 0. */
+int sm_mccbca_default_params(sm_mccbca_params* out);
+int sm_mccbca_arms_device(sm_ctx* ctx, const uint8_t* d_gray, int n, size_t image_stride, int H, int W, size_t row_stride,
+                          const sm_mccbca_params* params, uint8_t* d_arms);
+int sm_mccbca_aggregate_device(sm_ctx* ctx, const float* d_vol, const uint8_t* d_a, const uint8_t* d_b, int n,
+                               size_t image_stride, int H, int W, size_t row_stride, int D, int min_disparity,
+                               const sm_mccbca_params* params, int iterations, float* d_agg);
+/* Host pointers in and out (images packed: rows W bytes, images H * W bytes apart). */
+int sm_mccbca_arms(sm_ctx* ctx, const uint8_t* gray, int n, int H, int W, const sm_mccbca_params* params, uint8_t* arms);
+int sm_mccbca_aggregate(sm_ctx* ctx, const float* vol, const uint8_t* a, const uint8_t* b, int n, int H, int W, int D,
+                        int min_disparity, const sm_mccbca_params* params, int iterations, float* agg);
+/* The CPU twin of the two steps. */
+int sm_mccbca_arms_host(const uint8_t* gray, int n, size_t image_stride, int H, int W, size_t row_stride,
+                        const sm_mccbca_params* params, uint8_t* arms);
+int sm_mccbca_aggregate_host(const float* vol, const uint8_t* a, const uint8_t* b, int n, size_t image_stride, int H,
+                             int W, size_t row_stride, int D, int min_disparity, const sm_mccbca_params* params,
+                             int iterations, float* agg);
+
 /* Last error text of ctx (or of the calling thread when ctx == NULL). */
 const char* sm_last_error(sm_ctx* ctx);
 

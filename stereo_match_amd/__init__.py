@@ -26,7 +26,9 @@ Public surface (mirrors the reference / OpenCV names the reference uses):
   :meth:`StereoSGBM.computeFromCost` (``mc_cnn/script.py:9``, ``mapTo3D_mc_cnn.py:71``)
 * :class:`McCnnStereo`, :func:`mc_aggregate`, :func:`mc_disparity`, :class:`McCnnStereoParams` — mc-cnn's
   own stereo method on that volume: its SGM, left-right interpolation, sub-pixel step, median and
-  bilateral filter, up to the disparity maps ``mapTo3D_mc_cnn.py:70-77`` reads
+  bilateral filter, up to the disparity maps ``mapTo3D_mc_cnn.py:70-77`` reads;
+  :class:`McCnnCrossParams`, :func:`mc_cross_aggregate`, :func:`mc_cross_arms` — its cross-based cost
+  aggregation, off unless ``McCnnStereo(..., cross=...)`` asks for it
 
 All compute runs in ``libstereo_match_amd.so`` (HIP, gfx950) through the
 C-ABI in ``include/stereo_match_amd.h``; there is no CPU fallback.
@@ -49,7 +51,8 @@ from .filters import gaussian_filter, image_measure, pyrDown
 from . import mccnn
 from .mccnn import McCnnFast
 from . import mcstereo
-from .mcstereo import McCnnStereo, McCnnStereoParams, mc_aggregate, mc_disparity
+from .mcstereo import (McCnnCrossParams, McCnnStereo, McCnnStereoParams, mc_aggregate, mc_cross_aggregate, mc_cross_arms,
+                       mc_disparity)
 
 __all__ = [
     "compute_disparity", "matcher_from_settings", "StereoSGBM", "StereoSGBM_create", "createRightMatcher",
@@ -65,5 +68,6 @@ __all__ = [
     "filters", "gaussian_filter", "image_measure", "pyrDown",
     "mccnn", "McCnnFast",
     "mcstereo", "McCnnStereo", "McCnnStereoParams", "mc_aggregate", "mc_disparity",
+    "McCnnCrossParams", "mc_cross_arms", "mc_cross_aggregate",
 ]
 __version__ = "0.1.0"

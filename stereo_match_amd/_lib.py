@@ -108,6 +108,12 @@ class SmMcsgmStages(ctypes.Structure):
     _fields_ = [(n, ctypes.c_void_p) for n in ("wta_left", "wta_right", "status", "filled", "subpixel", "median")]
 
 
+class SmMccbcaParams(ctypes.Structure):
+    """Mirror of ``struct sm_mccbca_params`` (cross-based cost aggregation: arm length and threshold,
+    iterations before and after the semi-global matching)."""
+    _fields_ = [("l1", ctypes.c_int), ("tau1", ctypes.c_float), ("i1", ctypes.c_int), ("i2", ctypes.c_int)]
+
+
 MCSGM_STAGES = tuple(n for n, _ in SmMcsgmStages._fields_)
 MCSGM_INT_STAGES = MCSGM_STAGES[:4]  # int32 maps; the other two are float32
 
@@ -281,6 +287,21 @@ _SIGS = {
     "sm_mcsgm_disparity_host": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_size_t, _c.c_int,
                                            _c.c_int, _c.c_size_t, _c.c_int, _c.c_int, _c.POINTER(SmMcsgmParams),
                                            _c.c_void_p, _c.POINTER(SmMcsgmStages)]),
+    "sm_mccbca_default_params": (_c.c_int, [_c.POINTER(SmMccbcaParams)]),
+    "sm_mccbca_arms_device": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_size_t, _c.c_int, _c.c_int, _c.c_size_t,
+                                         _c.POINTER(SmMccbcaParams), _c.c_void_p]),
+    "sm_mccbca_aggregate_device": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_size_t,
+                                              _c.c_int, _c.c_int, _c.c_size_t, _c.c_int, _c.c_int,
+                                              _c.POINTER(SmMccbcaParams), _c.c_int, _c.c_void_p]),
+    "sm_mccbca_arms": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(SmMccbcaParams),
+                                  _c.c_void_p]),
+    "sm_mccbca_aggregate": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int,
+                                       _c.c_int, _c.c_int, _c.POINTER(SmMccbcaParams), _c.c_int, _c.c_void_p]),
+    "sm_mccbca_arms_host": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_size_t, _c.c_int, _c.c_int, _c.c_size_t,
+                                       _c.POINTER(SmMccbcaParams), _c.c_void_p]),
+    "sm_mccbca_aggregate_host": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_size_t, _c.c_int,
+                                            _c.c_int, _c.c_size_t, _c.c_int, _c.c_int, _c.POINTER(SmMccbcaParams),
+                                            _c.c_int, _c.c_void_p]),
     "sm_bm_default_params": (_c.c_int, [_c.c_int, _c.c_int, _c.POINTER(SmBmParams)]),
     "sm_bm_right_matcher_params": (_c.c_int, [_c.POINTER(SmBmParams), _c.POINTER(SmBmParams)]),
     "sm_bm_compute": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int,
@@ -511,6 +532,30 @@ def mcsgm_disparity_host(agg_l: np.ndarray, agg_r: np.ndarray, a: np.ndarray, im
     if rc != SM_OK:
         _raise(rc, None)
     return disp, maps
+
+
+def mccbca_arms_host(img: np.ndarray, image_stride: int, row_stride: int, prm: "SmMccbcaParams") -> np.ndarray:
+    """sm_mccbca_arms_host: uint8 [n, 4, H, W] (left, right, up, down) of the n images inside ``img``
+    (uint8 [n, H, W] of any row and image stride)."""
+    n, H, W = img.shape
+    arms = np.empty((n, 4, H, W), np.uint8)
+    rc = load().sm_mccbca_arms_host(img.ctypes.data, n, image_stride, H, W, row_stride, ctypes.byref(prm), arms.ctypes.data)
+    if rc != SM_OK:
+        _raise(rc, None)
+    return arms
+
+
+def mccbca_aggregate_host(vol: np.ndarray, a: np.ndarray, b: np.ndarray, image_stride: int, row_stride: int,
+                          min_disparity: int, prm: "SmMccbcaParams", iterations: int) -> np.ndarray:
+    """sm_mccbca_aggregate_host: the CPU twin's cross-based aggregation of ``vol`` [n, D, H, W] (float32,
+    contiguous) and the n images inside ``a`` / ``b`` (uint8; one geometry for both)."""
+    n, D, H, W = vol.shape
+    agg = np.empty_like(vol)
+    rc = load().sm_mccbca_aggregate_host(vol.ctypes.data, a.ctypes.data, b.ctypes.data, n, image_stride, H, W, row_stride,
+                                         D, min_disparity, ctypes.byref(prm), iterations, agg.ctypes.data)
+    if rc != SM_OK:
+        _raise(rc, None)
+    return agg
 
 
 def volume_scale(scale) -> float:
@@ -1016,6 +1061,33 @@ class Engine:
         self._check(self._lib.sm_mcsgm_disparity_device(self.ctx, d_agg_l, d_agg_r, d_a, n, image_stride, H, W, row_stride,
                                                         D, min_disparity, ctypes.byref(prm), d_disp,
                                                         ctypes.byref(stages) if stages is not None else None))
+
+    def mccbca_arms(self, img: np.ndarray, prm: "SmMccbcaParams") -> np.ndarray:
+        """sm_mccbca_arms: contiguous uint8 [n, H, W] -> uint8 [n, 4, H, W] (left, right, up, down)."""
+        n, H, W = img.shape
+        arms = np.empty((n, 4, H, W), np.uint8)
+        self._check(self._lib.sm_mccbca_arms(self.ctx, img.ctypes.data, n, H, W, ctypes.byref(prm), arms.ctypes.data))
+        return arms
+
+    def mccbca_aggregate(self, vol: np.ndarray, a: np.ndarray, b: np.ndarray, min_disparity: int,
+                         prm: "SmMccbcaParams", iterations: int) -> np.ndarray:
+        """sm_mccbca_aggregate: contiguous float32 [n, D, H, W] and uint8 [n, H, W] images."""
+        n, D, H, W = vol.shape
+        agg = np.empty_like(vol)
+        self._check(self._lib.sm_mccbca_aggregate(self.ctx, vol.ctypes.data, a.ctypes.data, b.ctypes.data, n, H, W, D,
+                                                  min_disparity, ctypes.byref(prm), iterations, agg.ctypes.data))
+        return agg
+
+    def mccbca_arms_device(self, d_gray: int, n: int, image_stride: int, H: int, W: int, row_stride: int,
+                           prm: "SmMccbcaParams", d_arms: int):
+        self._check(self._lib.sm_mccbca_arms_device(self.ctx, d_gray, n, image_stride, H, W, row_stride, ctypes.byref(prm),
+                                                    d_arms))
+
+    def mccbca_aggregate_device(self, d_vol: int, d_a: int, d_b: int, n: int, image_stride: int, H: int, W: int,
+                                row_stride: int, D: int, min_disparity: int, prm: "SmMccbcaParams", iterations: int,
+                                d_agg: int):
+        self._check(self._lib.sm_mccbca_aggregate_device(self.ctx, d_vol, d_a, d_b, n, image_stride, H, W, row_stride, D,
+                                                         min_disparity, ctypes.byref(prm), iterations, d_agg))
 
     def nlm_denoise(self, src: np.ndarray, h: float, template_window: int, search_window: int,
                     dst: np.ndarray = None) -> np.ndarray:

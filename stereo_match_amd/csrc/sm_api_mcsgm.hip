@@ -8,8 +8,6 @@
 #include "sm_ctx.hpp"
 #include "sm_mcsgm.hpp"
 
-extern "C" {
-
 // ---- MC-CNN's stereo method (sm_mcsgm.hpp)
 namespace {
 
@@ -59,6 +57,9 @@ int mcsgm_check_disparity(sm_ctx* ctx, const sm_mcsgm_params* p, int D, int m)
 
 smk::McsPen penalties(const sm_mcsgm_params* p) { return smk::mcs_penalties(p->pi1, p->pi2, p->sgm_q1, p->sgm_q2, p->sgm_v, p->sgm_d); }
 
+}  // namespace
+
+// (declared in sm_ctx.hpp: sm_api_mccbca.hip calls it too)
 // normalised float32 images of `sets` groups of n images each into dst[s] ([n][H][W]): the images'
 // sums, one wait for them, the tables from the host's float64 expression (the twin's by
 // construction), one upload
@@ -97,6 +98,8 @@ int mcsgm_normalise(sm_ctx* ctx, int sets, const uint8_t* const* d_gray, int n, 
     return SM_OK;
 }
 
+namespace {
+
 void launch_horz(sm_ctx* ctx, const smk::McsAggArgs& a)
 {
     const int nj = a.D <= 64 ? 1 : a.D <= 128 ? 2 : 4;
@@ -110,6 +113,8 @@ void launch_horz(sm_ctx* ctx, const smk::McsAggArgs& a)
 }
 
 }  // namespace
+
+extern "C" {
 
 int sm_mcsgm_default_params(sm_mcsgm_params* out)
 {

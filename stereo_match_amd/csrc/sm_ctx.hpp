@@ -1,6 +1,6 @@
 // sm_ctx.hpp — the host-side context of the C-ABI, shared by its translation units
 // (sm_api.hip: the matcher core; sm_api_image.hip, sm_api_cloud.hip, sm_api_png.hip,
-// sm_api_jpeg.hip, sm_api_mccnn.hip, sm_api_mcsgm.hip: the leaf subsystems).  Host code only: every kernel header is compiled
+// sm_api_jpeg.hip, sm_api_mccnn.hip, sm_api_mcsgm.hip, sm_api_mccbca.hip: the leaf subsystems).  Host code only: every kernel header is compiled
 // in exactly one unit (sm_paths.hpp, all templates, also in sm_deep.hip's), so none is included here.  fail, ensure, get_event, stage_in,
 // stage_out and check_sweep_errors are defined once, in sm_api.hip.
 #pragma once
@@ -104,6 +104,12 @@ struct sm_ctx {
         uint32_t sigma_bits = 0;
         int R = -1;
     } mcsgm;
+    // cross-based cost aggregation (sm_mccbca.hpp): the normalised images, their packed arms, the
+    // volume between two iterations; image, volumes and results of the host-pointer calls
+    struct {
+        DevBuf ta, tb, arms_a, arms_b, iter;
+        DevBuf in_vol, in_a, in_b, out;
+    } mccbca;
     struct { DevBuf a; } filter;  // image_measure: the first Gaussian's result, [img][H][W] float64
     DevBuf wls_num, wls_den, wls_inter, wls_w, wls_disp[2], wls_out;  // WLS scratch
     DevBuf wls_R, wls_IT;         // WLS: Thomas pivots / elimination factors of every pass
@@ -283,6 +289,12 @@ int stage_in(sm_ctx* ctx, std::initializer_list<StageCopy> copies);
 // copies out those with a host pointer, in order, as one timed SM_STAGE_D2H group, and waits
 // for the stream
 int stage_out(sm_ctx* ctx, std::initializer_list<StageCopy> copies);
+
+// sm_api_mcsgm.hip: the normalised float32 images (§4.18's grey-level table; a constant image is all
+// zeros) of `sets` groups of n images each into dst[s] ([n][H][W]), on the context's stream; waits
+// for the images' sums.  Shared with sm_api_mccbca.hip.
+int mcsgm_normalise(sm_ctx* ctx, int sets, const uint8_t* const* d_gray, int n, size_t image_stride, int H, int W,
+                    size_t row_stride, DevBuf* const* dst);
 
 // largest side of an image of the rectify, NLM and filter entry points
 constexpr int kRectMaxDim = 16384;

@@ -406,7 +406,7 @@ inline void mcsgm_disparity_host(const float* agg_l, const float* agg_r, const u
     }
 }
 
-#if defined(__HIPCC__)
+#if defined(__HIPCC__) && !defined(SM_MCSGM_NO_KERNELS)  // sm_mccbca.hpp's unit takes the host functions only
 // ---- kernels
 
 constexpr int MCS_BLOCK = 256;

@@ -1,13 +1,16 @@
-"""MC-CNN's stereo method after the matching cost: semi-global matching on the
-float32 volume of :class:`McCnnFast` with penalties that follow the intensity steps of both images,
-left-right interpolation, the sub-pixel step, a 5x5 median and a bilateral filter -- what turns the
-network's output into the ``left.png`` / ``right.png`` that ``mapTo3D_mc_cnn.py:70-77`` reads.
+"""MC-CNN's stereo method after the matching cost: cross-based cost
+aggregation (optional), semi-global matching on the float32 volume of :class:`McCnnFast` with
+penalties that follow the intensity steps of both images, left-right interpolation, the sub-pixel
+step, a 5x5 median and a bilateral filter -- what turns the network's output into the ``left.png``
+/ ``right.png`` that ``mapTo3D_mc_cnn.py:70-77`` reads.
 
 This is §4 of Žbontar & LeCun (JMLR 2016) restated; mc-cnn's own code is not available to this
-package, so parity with its output is **not** pinned, the default values are the paper's KITTI
-fast ones as recalled (unverified), and cross-based cost aggregation is not built.  What is pinned:
-the device and the CPU twin (``host=True``) give the same values, and the twin equals an
-independent numpy restatement.
+package, so parity with its output is **not** pinned (its cross-based aggregation may average the
+two axes one after the other where this one sums over the region, as the paper's equation does),
+and the default values are the paper's KITTI fast ones (:class:`McCnnStereoParams`) and KITTI
+accurate ones (:class:`McCnnCrossParams`) as recalled (unverified).  What is pinned: the device and
+the CPU twin (``host=True``) give the same values, and the twin equals an independent numpy
+restatement.
 """
 from __future__ import annotations
 
@@ -57,6 +60,31 @@ class McCnnStereoParams:
                                   self.blur_sigma, self.blur_t)
 
 
+@dataclasses.dataclass(frozen=True)
+class McCnnCrossParams:
+    """Cross-based cost aggregation: an arm grows while it stays inside the image,
+    is shorter than ``l1`` and the pixel differs from the arm's origin by less than ``tau1`` (on the
+    normalised image; rounded to float32); ``i1`` iterations run before the semi-global matching
+    and ``i2`` after it.  The defaults are the paper's KITTI accurate values as recalled
+    (unverified)."""
+    l1: int = 5
+    tau1: float = 0.13
+    i1: int = 2
+    i2: int = 0
+
+    def __post_init__(self):
+        for name, lo, hi in (("l1", 1, 32), ("i1", 0, 16), ("i2", 0, 16)):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer, float)) or int(v) != v or not lo <= int(v) <= hi:
+                raise ValueError(f"{name} {v!r}: an integer {lo} .. {hi}")
+        t = float(self.tau1)
+        if not math.isfinite(t) or not t > 0.0 or t > FLOAT32_MAX or float(np.float32(t)) == 0.0:
+            raise ValueError(f"tau1 {self.tau1!r} must be finite and positive")
+
+    def c_struct(self) -> "_lib.SmMccbcaParams":
+        return _lib.SmMccbcaParams(int(self.l1), self.tau1, int(self.i1), int(self.i2))
+
+
 def right_min_disparity(numDisparities: int, minDisparity: int) -> int:
     """``minDisparity`` of the right view's volume: ``-(minDisparity + numDisparities) + 1``."""
     return -(int(minDisparity) + int(numDisparities)) + 1
@@ -68,6 +96,20 @@ def _params(params):
     if not isinstance(params, McCnnStereoParams):
         raise ValueError("params must be a McCnnStereoParams")
     return params
+
+
+def _cross_params(params):
+    if params is None:
+        return McCnnCrossParams()
+    if not isinstance(params, McCnnCrossParams):
+        raise ValueError("params must be a McCnnCrossParams")
+    return params
+
+
+def _iterations(n):
+    if isinstance(n, bool) or int(n) != n or not 1 <= int(n) <= 16:
+        raise ValueError(f"iterations {n!r}: an integer 1 .. 16")
+    return int(n)
 
 
 def _offset(m):
@@ -153,6 +195,64 @@ def mc_aggregate(vol, a, b, minDisparity: int = 0, params: McCnnStereoParams = N
     return agg[0] if single else agg
 
 
+def mc_cross_arms(img, params: McCnnCrossParams = None, host: bool = False):
+    """The arms of every pixel of ``img`` (uint8 ``[H, W]`` or ``[N, H, W]``): uint8 ``[4, H, W]``
+    (``[N, 4, H, W]``) in the order left, right, up, down.  numpy in -> numpy out, a CUDA tensor
+    stays on the device on torch's current stream.  ``host=True``: the CPU twin (numpy only)."""
+    prm = _cross_params(params).c_struct()
+    if _is_torch_cuda(img):
+        import torch
+
+        if host:
+            raise ValueError("host=True takes numpy arrays")
+        t3 = McCnnFast._torch_images(img)[0]
+        n, H, W = t3.shape
+        eng = _lib.engine(t3.device.index or 0)
+        eng.set_stream(torch.cuda.current_stream(t3.device).cuda_stream)
+        arms = torch.empty((n, 4, H, W), dtype=torch.uint8, device=t3.device)
+        eng.mccbca_arms_device(t3.data_ptr(), n, t3.stride(0), H, W, t3.stride(1), prm, arms.data_ptr())
+        return arms[0] if img.dim() == 2 else arms
+    a = np.asarray(img)
+    if a.dtype != np.uint8 or a.ndim not in (2, 3) or a.size == 0:
+        raise ValueError("img must be a non-empty uint8 gray array [H, W] or [N, H, W]")
+    a3 = np.ascontiguousarray(a[None] if a.ndim == 2 else a)
+    n, H, W = a3.shape
+    arms = _lib.mccbca_arms_host(a3, H * W, W, prm) if host else _lib.engine(0).mccbca_arms(a3, prm)
+    return arms[0] if a.ndim == 2 else arms
+
+
+def mc_cross_aggregate(vol, a, b, minDisparity: int = 0, params: McCnnCrossParams = None, iterations: int = 1,
+                       host: bool = False):
+    """``iterations`` steps of the cross-based cost aggregation of ``vol`` (float32 ``[D, H, W]`` or
+    ``[N, D, H, W]``, what ``McCnnFast.cost_volume(a, b, D, minDisparity)`` returns): ``a`` is the view's
+    own uint8 image, ``b`` the other one.  Uses ``l1`` and ``tau1`` of ``params``.  Returns a new volume
+    of the same shape; numpy in -> numpy out, CUDA tensors stay on the device on torch's current
+    stream.  ``host=True``: the CPU twin (numpy only)."""
+    prm, m, it = _cross_params(params).c_struct(), _offset(minDisparity), _iterations(iterations)
+    if _is_torch_cuda(vol):
+        import torch
+
+        if host:
+            raise ValueError("host=True takes numpy arrays")
+        v4, single = _torch_volume(vol, "vol")
+        n, D, H, W = v4.shape
+        a3, b3 = _torch_images((a, b), (n, H, W), v4.device)
+        eng = _lib.engine(v4.device.index or 0)
+        eng.set_stream(torch.cuda.current_stream(v4.device).cuda_stream)
+        agg = torch.empty_like(v4)
+        eng.mccbca_aggregate_device(v4.data_ptr(), a3.data_ptr(), b3.data_ptr(), n, a3.stride(0), H, W, a3.stride(1), D, m,
+                                    prm, it, agg.data_ptr())
+        return agg[0] if single else agg
+    v4, single = _np_volume(vol, "vol")
+    n, D, H, W = v4.shape
+    a3, b3 = (np.ascontiguousarray(_np_images(x, (n, H, W), w)) for x, w in ((a, "a"), (b, "b")))
+    if host:
+        agg = _lib.mccbca_aggregate_host(v4, a3, b3, H * W, W, m, prm, it)
+    else:
+        agg = _lib.engine(0).mccbca_aggregate(v4, a3, b3, m, prm, it)
+    return agg[0] if single else agg
+
+
 def mc_disparity(agg_l, agg_r, a_l, minDisparity: int = 0, params: McCnnStereoParams = None, host: bool = False,
                  stages: bool = False):
     """The left view's disparity map, float32 ``[H, W]`` (``[N, H, W]`` for batches), from the two
@@ -209,16 +309,29 @@ def _check_offset_range(m, D):
 
 
 class McCnnStereo:
-    """``McCnnStereo(net, params).compute(left, right, numDisparities, minDisparity=0)``: the
-    features once, the volumes of both views, both aggregations, the disparity.  Returns
+    """``McCnnStereo(net, params, cross).compute(left, right, numDisparities, minDisparity=0)``: the
+    features once, the volumes of both views, both aggregations, the disparity.  ``cross`` (a
+    :class:`McCnnCrossParams`; None: none) adds the cross-based cost aggregation to both views: ``i1``
+    iterations before the semi-global matching and ``i2`` after it.  Returns
     ``(disp_left, disp_right_wta)``: the finished left map and the right view's winner-take-all
     disparities as float32 (what the left-right check compared against), both with invalid pixels at
     ``float(minDisparity - 1)``."""
 
-    def __init__(self, net: McCnnFast, params: McCnnStereoParams = None):
+    def __init__(self, net: McCnnFast, params: McCnnStereoParams = None, cross: McCnnCrossParams = None):
         if not isinstance(net, McCnnFast):
             raise ValueError("net must be a McCnnFast")
         self.net, self.params = net, _params(params)
+        self.cross = None if cross is None else _cross_params(cross)
+
+    def _aggregate(self, vol, a, b, m, host):
+        """One view: i1 cross-based iterations, the semi-global matching, i2 more."""
+        cross = self.cross
+        if cross is not None and cross.i1:
+            vol = mc_cross_aggregate(vol, a, b, m, cross, cross.i1, host=host)
+        vol = mc_aggregate(vol, a, b, m, self.params, host=host)
+        if cross is not None and cross.i2:
+            vol = mc_cross_aggregate(vol, a, b, m, cross, cross.i2, host=host)
+        return vol
 
     def compute(self, left, right, numDisparities, minDisparity: int = 0, host: bool = False):
         net = self.net
@@ -230,8 +343,8 @@ class McCnnStereo:
             raise ValueError("the two images must have the same shape")
         m_r = right_min_disparity(D, m)
         fl, fr = net.features(left, host=host), net.features(right, host=host)
-        agg_l = mc_aggregate(net.join(fl, fr, D, m, host=host), left, right, m, self.params, host=host)
-        agg_r = mc_aggregate(net.join(fr, fl, D, m_r, host=host), right, left, m_r, self.params, host=host)
+        agg_l = self._aggregate(net.join(fl, fr, D, m, host=host), left, right, m, host)
+        agg_r = self._aggregate(net.join(fr, fl, D, m_r, host=host), right, left, m_r, host)
         disp, maps = mc_disparity(agg_l, agg_r, left, m, self.params, host=host, stages=True)
         right_wta = maps["wta_right"]
         right_wta = right_wta.float() if _is_torch_cuda(right_wta) else right_wta.astype(np.float32)
