@@ -206,7 +206,9 @@ int sm_filter_speckles_device(sm_ctx* ctx, int16_t* d_img, int nimg, int H, int 
  * reference reprojects the filtered int16 map (disparity_calculation.py:302;
  * mapTo3D_mc_cnn.py:124 with float32) — xyz out float32 [H][W][3].
  * Q: 4x4 row-major float64.  Host version synchronous; the device version
- * handles nimg maps (disp + i*H*W, xyz + i*H*W*3). */
+ * handles nimg maps (disp + i*H*W, xyz + i*H*W*3).  handle_missing: Z = 10000 within FLT_EPSILON
+ * of the map's minimum, the one a compare-based scan finds: a NaN pixel of either sign and any
+ * payload takes no part in it, and a map without a non-NaN pixel marks nothing. */
 #define SM_DISP_S16 0
 #define SM_DISP_F32 1
 int sm_reproject_image_to_3d(sm_ctx* ctx, const void* disp, int disp_type, int H, int W, const double* Q,
@@ -320,7 +322,8 @@ int sm_pyr_down_u8_batch_device(sm_ctx* ctx, const uint8_t* d_src, int nimg, siz
  * points[mask] / colors[mask], and the rows io_functions.write_ply writes (io_functions.py:28-44).
  *
  * Mask: lo < d < hi, strict; either bound may be absent.  SM_CLOUD_LO_MIN takes lo from the map
- * itself, one minimum per image (try_try.py:92; a NaN-free map).  A NaN
+ * itself, one minimum per image, as numpy's `d > d.min()` (try_try.py:92): a map with a NaN
+ * pixel, of either sign, has the bound NaN and an empty cloud.  A NaN
  * disparity passes no bound.  For a float32 map a bound is rounded to float32 before it is
  * compared, as numpy >= 2 does with a Python scalar; an int16 map compares as the numbers they
  * are.  A NaN bound is SM_E_ARG.  zero_nonfinite replaces every NaN or +-inf COMPONENT by 0

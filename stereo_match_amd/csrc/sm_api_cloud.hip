@@ -11,6 +11,32 @@
 #include "sm_reproject.hpp"
 #include "sm_cloud.hpp"
 
+namespace {
+
+// the maps' minima on the ctx stream (k_disp_min, k_keys_to_float): mn[img] is the minimum of
+// the non-NaN pixels (handleMissingValues), lo[img] numpy's `d.min()` (lo = "min"; may be NULL).
+// ctx->rp.min: int keys [2][nimg], then float [2][nimg].
+int disp_minima_enqueue(sm_ctx* ctx, const void* d_disp, int disp_type, int nimg, size_t npx, const float** mn,
+                        const float** lo)
+{
+    int rc;
+    if ((rc = ensure(ctx, ctx->rp.min, (size_t)nimg * 16)) != SM_OK) return rc;
+    int* keys = (int*)ctx->rp.min.p;
+    float* out = (float*)(keys + 2 * (size_t)nimg);
+    HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)keys, smk::KEY_NONE, 2 * (size_t)nimg, ctx->stream));
+    const dim3 g((unsigned)std::min<size_t>((npx + 255) / 256, 1024), nimg);
+    if (disp_type == SM_DISP_S16)
+        hipLaunchKernelGGL(smk::k_disp_min<int16_t>, g, dim3(256), 0, ctx->stream, (const int16_t*)d_disp, keys, npx);
+    else
+        hipLaunchKernelGGL(smk::k_disp_min<float>, g, dim3(256), 0, ctx->stream, (const float*)d_disp, keys, npx);
+    hipLaunchKernelGGL(smk::k_keys_to_float, dim3((nimg + 63) / 64), dim3(64), 0, ctx->stream, keys, out, nimg);
+    *mn = out;
+    if (lo) *lo = out + nimg;
+    return SM_OK;
+}
+
+}  // namespace
+
 extern "C" {
 
 int sm_reproject_image_to_3d_device(sm_ctx* ctx, const void* d_disp, int disp_type, int nimg, int H, int W,
@@ -32,17 +58,7 @@ int sm_reproject_image_to_3d_device(sm_ctx* ctx, const void* d_disp, int disp_ty
     const size_t npx = (size_t)H * W;
     if (ra.handle_missing) {
         int rc;
-        if ((rc = ensure(ctx, ctx->rp.min, (size_t)nimg * 8)) != SM_OK) return rc;
-        int* keys = (int*)ctx->rp.min.p;
-        HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)keys, 0x7FFFFFFF, nimg, ctx->stream));
-        const dim3 g((unsigned)std::min<size_t>((npx + 255) / 256, 1024), nimg);
-        if (disp_type == SM_DISP_S16)
-            hipLaunchKernelGGL(smk::k_disp_min<int16_t>, g, dim3(256), 0, ctx->stream, (const int16_t*)d_disp, keys, npx);
-        else
-            hipLaunchKernelGGL(smk::k_disp_min<float>, g, dim3(256), 0, ctx->stream, (const float*)d_disp, keys, npx);
-        hipLaunchKernelGGL(smk::k_keys_to_float, dim3((nimg + 63) / 64), dim3(64), 0, ctx->stream, keys,
-                           (float*)(keys + nimg), nimg);
-        ra.min_disp = (const float*)(keys + nimg);
+        if ((rc = disp_minima_enqueue(ctx, d_disp, disp_type, nimg, npx, &ra.min_disp, nullptr)) != SM_OK) return rc;
     }
     const dim3 grid((W + 255) / 256, H, nimg);
     if (disp_type == SM_DISP_S16)
@@ -130,18 +146,10 @@ int cloud_extract_enqueue(sm_ctx* ctx, const void* d_disp, int disp_type, const 
     a.handle_missing = p->handle_missing != 0, a.zero_nonfinite = p->zero_nonfinite != 0;
     const bool s16 = disp_type == SM_DISP_S16;
     if (a.handle_missing || p->lo_mode == SM_CLOUD_LO_MIN) {
-        if ((rc = ensure(ctx, ctx->rp.min, (size_t)nimg * 8)) != SM_OK) return rc;
-        int* keys = (int*)ctx->rp.min.p;
-        HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)keys, 0x7FFFFFFF, nimg, ctx->stream));
-        const dim3 gm((unsigned)std::min<size_t>((g.npx + 255) / 256, 1024), nimg);
-        if (s16)
-            hipLaunchKernelGGL(smk::k_disp_min<int16_t>, gm, dim3(256), 0, ctx->stream, (const int16_t*)d_disp, keys, g.npx);
-        else
-            hipLaunchKernelGGL(smk::k_disp_min<float>, gm, dim3(256), 0, ctx->stream, (const float*)d_disp, keys, g.npx);
-        hipLaunchKernelGGL(smk::k_keys_to_float, dim3((nimg + 63) / 64), dim3(64), 0, ctx->stream, keys,
-                           (float*)(keys + nimg), nimg);
-        if (a.handle_missing) a.min_disp = (const float*)(keys + nimg);
-        if (p->lo_mode == SM_CLOUD_LO_MIN) a.lo_dev = (const float*)(keys + nimg);
+        const float *mn, *lo;
+        if ((rc = disp_minima_enqueue(ctx, d_disp, disp_type, nimg, g.npx, &mn, &lo)) != SM_OK) return rc;
+        if (a.handle_missing) a.min_disp = mn;
+        if (p->lo_mode == SM_CLOUD_LO_MIN) a.lo_dev = lo;
     }
     const dim3 grid(g.bpi, nimg), blk(smk::CLOUD_BLOCK);
     if (s16)

@@ -57,29 +57,51 @@ __global__ void __launch_bounds__(256) k_reproject(ReprojArgs a)
     reproject_point(a.Q, x, y, d, a.handle_missing, md, a.xyz + 3 * i);
 }
 
-// per-image minimum (handleMissingValues): order-preserving int key of float
+// per-image minimum (handleMissingValues, the cloud's lo = "min"): order-preserving int key of a
+// float.  The minimum is the one a compare-based scan finds (`if (v < min) min = v`): a NaN of
+// either sign and any payload takes no part in it.  Every NaN gets KEY_NONE, the key the
+// reduction starts from and above +inf's (0x7F800000), so no other value has it: a map without a
+// non-NaN pixel keeps KEY_NONE, which key_float turns into a NaN, and `|d - NaN| <= eps` marks
+// no pixel.  -0 sorts below +0; as a minimum the two are the same number.
+constexpr int KEY_NONE = 0x7FFFFFFF;
+
 __device__ inline int float_key(float f)
 {
     const int b = __float_as_int(f);
+    if ((b & 0x7FFFFFFF) > 0x7F800000) return KEY_NONE;
     return b >= 0 ? b : b ^ 0x7FFFFFFF;
 }
 __device__ inline float key_float(int k) { return __int_as_float(k >= 0 ? k : k ^ 0x7FFFFFFF); }
 
+// keys: [2][nimg], both rows initialised to KEY_NONE.  Row 0: the minimum's key.  Row 1: 0 once
+// any pixel of the image is a NaN (numpy's `d.min()` is then NaN), found in the same pass.
 template <typename T>
 __global__ void __launch_bounds__(256) k_disp_min(const T* disp, int* keys, size_t npx)
 {
-    const int img = blockIdx.y;
-    int m = 0x7FFFFFFF;
-    for (size_t i = blockIdx.x * 256 + threadIdx.x; i < npx; i += (size_t)gridDim.x * 256)
-        m = min(m, float_key(disp_value(disp, img * npx + i)));
+    const int img = blockIdx.y, nimg = gridDim.y;
+    int m = KEY_NONE;
+    bool nan = false;
+    for (size_t i = blockIdx.x * 256 + threadIdx.x; i < npx; i += (size_t)gridDim.x * 256) {
+        const int k = float_key(disp_value(disp, img * npx + i));
+        nan |= k == KEY_NONE;
+        m = min(m, k);
+    }
     for (int o = 32; o > 0; o >>= 1) m = min(m, __shfl_xor(m, o));
-    if ((threadIdx.x & 63) == 0) atomicMin(keys + img, m);
+    const bool wave_nan = __any(nan);
+    if ((threadIdx.x & 63) == 0) {
+        atomicMin(keys + img, m);
+        if (wave_nan) atomicMin(keys + nimg + img, 0);
+    }
 }
 
+// out: [2][n].  Row 0: the minimum of the non-NaN pixels (handleMissingValues).  Row 1: numpy's
+// `d.min()`, NaN when the image holds a NaN (the cloud's lo = "min": `d > NaN` passes nothing).
 __global__ void k_keys_to_float(const int* keys, float* out, int n)
 {
     const int i = blockIdx.x * 64 + threadIdx.x;
-    if (i < n) out[i] = key_float(keys[i]);
+    if (i >= n) return;
+    out[i] = key_float(keys[i]);
+    out[n + i] = key_float(keys[n + i] == 0 ? KEY_NONE : keys[i]);
 }
 
 }  // namespace smk

@@ -115,8 +115,10 @@ def extract_point_cloud(disparity, Q, image_bgr, lo=None, hi=None, *, zero_nonfi
 
     ``lo`` / ``hi``: strict bounds as Python scalars, compared as numpy >= 2 compares them (a
     float32 map with the bound rounded to float32, an int16 map exactly); ``None`` leaves a
-    bound out; ``lo="min"`` is the map's own minimum (``try_try.py:92``; per map in a batch; for
-    a NaN-free map).  A NaN disparity passes no bound; a NaN bound is a ``ValueError``.
+    bound out; ``lo="min"`` is the map's own minimum (``try_try.py:92``; per map in a batch) as
+    numpy's ``d > d.min()``: a map with a NaN pixel, of either sign, gives an empty cloud.
+    ``handleMissingValues`` takes its minimum over the non-NaN pixels, as ``reprojectImageTo3D``.
+    A NaN disparity passes no bound; a NaN bound is a ``ValueError``.
     ``zero_nonfinite`` replaces every NaN or infinite component by 0
     (``disparity_calculation.py:316-317``).
 

@@ -35,7 +35,9 @@ def _is_torch_cuda(x) -> bool:
 def reprojectImageTo3D(disparity, Q, _3dImage=None, handleMissingValues=False, ddepth=-1, device=0):
     """float32 ``[H, W, 3]`` points.  ``disparity``: int16 or float32 (numpy, or
     a torch CUDA tensor → CUDA tensor on torch's current stream).  Only
-    ``ddepth`` -1 / CV_32F (5) is implemented (what the reference uses)."""
+    ``ddepth`` -1 / CV_32F (5) is implemented (what the reference uses).
+    ``handleMissingValues``: Z = 10000 within FLT_EPSILON of the map's minimum;
+    a NaN pixel (either sign, any payload) takes no part in the minimum."""
     if ddepth not in (-1, 5):
         raise _lib.SmError(_lib.SM_E_UNSUPPORTED, "reprojectImageTo3D: only ddepth=CV_32F is implemented")
     Qd = np.ascontiguousarray(np.asarray(Q, np.float64).reshape(4, 4))

@@ -9,6 +9,7 @@ import io
 import numpy as np
 import pytest
 
+import reproject_cases as C
 import stereo_match_amd as sma
 from oracle import reproject_np
 from stereo_match_amd import _lib, synthetic
@@ -59,7 +60,8 @@ def _image(H, W, seed=5):
 
 
 def numpy_mask(d, lo, hi):
-    """The mask as the scripts write it, numpy's own comparison with Python scalars."""
+    """The mask as the scripts write it, numpy's own comparison with Python scalars.  `d.min()` of
+    a map with a NaN pixel is NaN and passes nothing: rule 2 of oracle/reproject_np.py."""
     m = np.ones(d.shape, bool)
     if isinstance(lo, str):
         m &= d > d.min()
@@ -189,6 +191,118 @@ def test_float_map_with_nan_pixels(lo, hi):
         assert_fraction(m)
         assert not m[nan].any()
     assert_cloud(sma.extract_point_cloud(d, Q_CALC, img, lo, hi), pts, rgb)
+
+
+# ---- NaN pixels where a minimum is taken (the two rules of oracle/reproject_np.py).
+# Neither may depend on the NaNs' sign or payload.
+@functools.lru_cache(maxsize=None)
+def _nan_map(sign, H=130, W=150, payloads=C.NAN_PAYLOADS):
+    """_map's float32 map (minimum -1) with the float32 successor of the minimum at pixel 1 -- above
+    the minimum, inside the FLT_EPSILON window -- and NaNs of one sign: the first pixel, the
+    last, and every 23rd (lanes of every kind), their payloads cycling through `payloads`."""
+    d = _map(H, W, "f32").copy()
+    d.flat[1] = np.nextafter(np.float32(-1), np.float32(0))
+    if sign:
+        C.put_nans(d, [0, H * W - 1] + list(range(40, H * W, 23)), sign, payloads)
+    d.setflags(write=False)
+    return d
+
+
+def _empty_header():
+    return (sma.reproject.PLY_HEADER % dict(vert_num=0)).encode()
+
+
+@pytest.mark.parametrize("hi", [None, 15.7])
+@pytest.mark.parametrize("payloads", [C.NAN_PAYLOADS, C.QUIET_ONLY], ids=["payloads", "np.nan"])
+@pytest.mark.parametrize("sign", [+1, -1])
+def test_nan_map_lo_min_is_an_empty_cloud(sign, payloads, hi, tmp_path):
+    """Rule 2: `d > d.min()` with a NaN pixel is `d > NaN`, for np.nan itself (0x7FC00000), its
+    negative and every other payload."""
+    import torch
+
+    d, img = _nan_map(sign, payloads=payloads), _image(130, 150)
+    pts, rgb, m = expected(d, Q_CALC, img, "min", hi)
+    assert np.isnan(d.min()) and not m.any()
+    got = sma.extract_point_cloud(d, Q_CALC, img, "min", hi)
+    assert got[0].shape == (0, 3) and got[1].shape == (0, 3)
+    assert_cloud(got, pts, rgb)
+    v, c = sma.extract_point_cloud(torch.from_numpy(d.copy()).cuda(), Q_CALC, torch.from_numpy(img.copy()).cuda(), "min", hi)
+    assert v.shape == (0, 3) and c.shape == (0, 3)
+    assert sma.write_point_cloud(str(tmp_path / "a.ply"), d, Q_CALC, img, "min", hi) == 0
+    assert (tmp_path / "a.ply").read_bytes() == _empty_header()
+    n = sma.write_point_cloud(str(tmp_path / "b.ply"), torch.from_numpy(d.copy()).cuda(), Q_CALC,
+                              torch.from_numpy(img.copy()).cuda(), "min", hi)
+    assert n == 0 and (tmp_path / "b.ply").read_bytes() == _empty_header()
+
+
+@pytest.mark.parametrize("lo,hi", [(-1.5, None), (-1.5, 15.7), (None, 15.7), (None, None)])
+def test_nan_map_handle_missing_follows_rule_1(lo, hi):
+    """Rule 1, vertex for vertex: the NaNs take no part in the minimum, so the pixels at -1 and its
+    successor get Z = 10000, whatever the NaNs' sign."""
+    img = _image(130, 150)
+    got = []
+    for sign in (+1, -1):
+        d = _nan_map(sign)
+        pts, rgb, m = expected(d, Q_CALC, img, lo, hi, hm=True)
+        n_marked = int((pts[:, 2] == 10000).sum())
+        assert n_marked == int((d <= d.flat[1]).sum()) > 100 and (pts[:, 2] != 10000).any()
+        if lo is None and hi is None:
+            assert m.all() and np.isnan(pts).any()
+        else:
+            assert 0.05 <= m.mean() < 1 and not m[np.isnan(d)].any()
+        got.append(sma.extract_point_cloud(d, Q_CALC, img, lo, hi, handleMissingValues=True))
+        assert_cloud(got[-1], pts, rgb)
+    assert_verts_equal(got[0][0], got[1][0])
+
+
+@pytest.mark.parametrize("sign", [0, +1, -1])
+def test_lo_min_with_handle_missing(sign):
+    """Both at once need both facts of a map: rule 1's minimum for the 10000s and numpy's `d.min()`
+    for the mask.  NaN-free (sign 0): the minimum's pixels fail `d > min`, its successor passes
+    and is marked.  With NaNs: empty."""
+    import torch
+
+    d, img = _nan_map(sign), _image(130, 150)
+    pts, rgb, m = expected(d, Q_CALC, img, "min", None, hm=True)
+    if sign:
+        assert not m.any()
+    else:
+        assert_fraction(m)
+        assert (pts[:, 2] == 10000).sum() == 1 and m.flat[1]
+    assert_cloud(sma.extract_point_cloud(d, Q_CALC, img, "min", handleMissingValues=True), pts, rgb)
+    v, c = sma.extract_point_cloud(torch.from_numpy(d.copy()).cuda(), Q_CALC, torch.from_numpy(img.copy()).cuda(), "min",
+                                   handleMissingValues=True)
+    assert_cloud((v.cpu().numpy(), c.cpu().numpy()), pts, rgb)
+
+
+@pytest.mark.parametrize("hm", [False, True])
+@pytest.mark.parametrize("sign", [+1, -1])
+def test_batch_device_only_one_map_has_a_nan(sign, hm):
+    """lo = "min" on the batch entry point: map 1's cloud is empty, its neighbours' are not, and
+    every map keeps its own minimum (-1, -1 with np.nan or its negative, 2.5)."""
+    import torch
+
+    H, W = 37, 53
+    maps = np.stack([_nan_map(0, H, W), _nan_map(sign, H, W, C.QUIET_ONLY), np.maximum(_map(H, W, "f32"), np.float32(2.5))])
+    imgs = np.stack([_image(H, W, 30 + i) for i in range(3)])
+    exp = [expected(maps[i], Q_CALC, imgs[i], "min", None, hm=hm) for i in range(3)]
+    want_counts = [int(e[2].sum()) for e in exp]
+    assert want_counts[1] == 0 and want_counts[0] > 0 and want_counts[2] > 0 and want_counts[0] != want_counts[2]
+    if hm:
+        assert (exp[0][0][:, 2] == 10000).sum() == 1 and not (exp[2][0][:, 2] == 10000).any()
+    v, c, counts = sma.extract_point_cloud(torch.from_numpy(maps).cuda(), Q_CALC, torch.from_numpy(imgs).cuda(), "min",
+                                           handleMissingValues=hm)
+    assert counts.tolist() == want_counts
+    assert_cloud((v.cpu().numpy(), c.cpu().numpy()), np.concatenate([e[0] for e in exp]),
+                 np.concatenate([e[1] for e in exp]))
+    # a numeric bound with handleMissingValues: map 1 follows rule 1 beside its neighbours
+    exp = [expected(maps[i], Q_CALC, imgs[i], -1.5, None, hm=True) for i in range(3)]
+    assert all((e[0][:, 2] == 10000).any() for e in exp)
+    v, c, counts = sma.extract_point_cloud(torch.from_numpy(maps).cuda(), Q_CALC, torch.from_numpy(imgs).cuda(), -1.5,
+                                           handleMissingValues=True)
+    assert counts.tolist() == [int(e[2].sum()) for e in exp]
+    assert_cloud((v.cpu().numpy(), c.cpu().numpy()), np.concatenate([e[0] for e in exp]),
+                 np.concatenate([e[1] for e in exp]))
 
 
 # ---- zero_nonfinite, strides
