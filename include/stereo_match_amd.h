@@ -795,6 +795,9 @@ int sm_set_debug_flags(sm_ctx* ctx, int flags);
  *                      v + 1, and the launch after 65535 clears the granules and restarts at 1.
  *                      v must be no smaller than the counter is (tags of later epochs would
  *                      otherwise read as fresh); 0 changes nothing.
+ *   SM_TUNE_MCACC_CHUNK cells (plane values) the accurate MC-CNN scorer runs per pass through its
+ *                      scratch buffers: 0 automatic (up to 2^20, bounded by a
+ *                      quarter of the free device memory), 1..2^22.  Any value gives the same bits.
  * Returns SM_E_ARG for an unknown key or value. */
 #define SM_TUNE_EW_LANES 1
 #define SM_TUNE_SWEEP_NCW 2
@@ -813,6 +816,7 @@ int sm_set_debug_flags(sm_ctx* ctx, int flags);
 #define SM_TUNE_EW_START 15
 #define SM_TUNE_EW_PATCH 16
 #define SM_TUNE_HOP_EPOCH 17
+#define SM_TUNE_MCACC_CHUNK 18
 int sm_set_tuning(sm_ctx* ctx, int key, int value);
 
 /* ---- MC-CNN fast matching cost: two gray images to the float32 cost volume
@@ -851,6 +855,45 @@ int sm_mccnn_features_host(int L, const float* const* w, const float* const* b, 
                            size_t image_stride, int H, int W, size_t row_stride, float* feat);
 int sm_mccnn_join_host(const float* feat_a, const float* feat_b, int n, int H, int W, int D, int min_disparity,
                        float* vol);
+
+/* ---- MC-CNN accurate matching cost: the 112-map feature net and the fully
+ * connected scorer.  Features: L (1..6) convolutions 3x3, zero padding 1, 112 feature maps, ReLU
+ * after every layer, no unit-length step; float32 [n][H][W][112], channel last.  Scorer: F (1..4)
+ * hidden layers of U units (a multiple of 32, 32..384) with ReLU, one linear unit, a sigmoid.
+ * Plane d of the volume at (y, x) is minus the sigmoid (raw != 0: minus the logit) of the scorer
+ * on image a's features at x and image b's at x - (min_disparity + d), NaN where that column is
+ * outside the image; a_is_left says which of the two feeds the left half of the first layer
+ * (columns 0..111 of fw[0]) -- the right view's volume is (a = right, b = left, a_is_left = 0,
+ * min_disparity = -(min_disparity + D) + 1).  Every value is one fixed chain of fused
+ * multiply-adds in ascending k (the first layer split into a per-pixel projection of each image
+ * and one float add per cell), so the device and the *_host functions give the same bits.
+ *
+ * Weights: w[0] float32 [112][1][3][3], w[i] [112][112][3][3], b[i] [112]; fw[0] [U][224],
+ * fw[1..F-1] [U][U], fw[F] [1][U] (nn.Linear's [out][in]), fb[i] [U], fb[F] [1].  Images,
+ * alignment, D, min_disparity and streams as for the fast net above; its weights in the same
+ * context are not disturbed.  The scorer works through scratch buffers of the context in chunks of
+ * cells (SM_TUNE_MCACC_CHUNK); their size is bounded and does not grow with H * W * D. */
+int sm_mcacc_set_weights(sm_ctx* ctx, int L, const float* const* w, const float* const* b, int F, int U,
+                         const float* const* fw, const float* const* fb);
+int sm_mcacc_features_device(sm_ctx* ctx, const uint8_t* d_gray, int n, size_t image_stride, int H, int W,
+                             size_t row_stride, float* d_feat);
+int sm_mcacc_join_device(sm_ctx* ctx, const float* d_feat_a, const float* d_feat_b, int n, int H, int W, int D,
+                         int min_disparity, int a_is_left, int raw, float* d_vol);
+int sm_mcacc_volume_device(sm_ctx* ctx, const uint8_t* d_a, const uint8_t* d_b, int n, size_t image_stride, int H,
+                           int W, size_t row_stride, int D, int min_disparity, int a_is_left, int raw, float* d_vol);
+/* Host pointers in and out (images packed: rows W bytes, images H * W bytes apart). */
+int sm_mcacc_features(sm_ctx* ctx, const uint8_t* gray, int n, int H, int W, float* feat);
+int sm_mcacc_join(sm_ctx* ctx, const float* feat_a, const float* feat_b, int n, int H, int W, int D,
+                  int min_disparity, int a_is_left, int raw, float* vol);
+int sm_mcacc_volume(sm_ctx* ctx, const uint8_t* a, const uint8_t* b, int n, int H, int W, int D, int min_disparity,
+                    int a_is_left, int raw, float* vol);
+/* The CPU twin of the two steps, and the scorer's sigmoid on n values. */
+int sm_mcacc_features_host(int L, const float* const* w, const float* const* b, const uint8_t* gray, int n,
+                           size_t image_stride, int H, int W, size_t row_stride, float* feat);
+int sm_mcacc_join_host(int F, int U, const float* const* fw, const float* const* fb, const float* feat_a,
+                       const float* feat_b, int n, int H, int W, int D, int min_disparity, int a_is_left, int raw,
+                       float* vol);
+int sm_mcacc_sigmoid_host(const float* z, size_t n, float* s);
 
 /* ---- MC-CNN's stereo method after the matching cost: the paper's semi-global
  * matching on the float32 volume, left-right interpolation, sub-pixel step, 5x5 median and

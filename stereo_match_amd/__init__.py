@@ -24,6 +24,8 @@ Public surface (mirrors the reference / OpenCV names the reference uses):
   ``disparity_test.py:79-80``, ``mapTo3D.py:78-79``), decoded on the device
 * :class:`McCnnFast` — the mc-cnn *fast* matching cost, images to the float32 cost volume of
   :meth:`StereoSGBM.computeFromCost` (``mc_cnn/script.py:9``, ``mapTo3D_mc_cnn.py:71``)
+* :class:`McCnnAccurate` — the mc-cnn *accurate* matching cost (112-map features, a fully connected
+  scorer and a sigmoid; ``mc_cnn/script.py:10``), the same volume for :class:`McCnnStereo`
 * :class:`McCnnStereo`, :func:`mc_aggregate`, :func:`mc_disparity`, :class:`McCnnStereoParams` — mc-cnn's
   own stereo method on that volume: its SGM, left-right interpolation, sub-pixel step, median and
   bilateral filter, up to the disparity maps ``mapTo3D_mc_cnn.py:70-77`` reads;
@@ -50,6 +52,8 @@ from . import filters
 from .filters import gaussian_filter, image_measure, pyrDown
 from . import mccnn
 from .mccnn import McCnnFast
+from . import mcaccurate
+from .mcaccurate import McCnnAccurate
 from . import mcstereo
 from .mcstereo import (McCnnCrossParams, McCnnStereo, McCnnStereoParams, mc_aggregate, mc_cross_aggregate, mc_cross_arms,
                        mc_disparity)
@@ -66,7 +70,7 @@ __all__ = [
     "encode_disparity_png", "imread", "imdecode", "imdecode_batch", "imdecode_host", "read_disparity_png",
     "decode_disparity_png",
     "filters", "gaussian_filter", "image_measure", "pyrDown",
-    "mccnn", "McCnnFast",
+    "mccnn", "McCnnFast", "mcaccurate", "McCnnAccurate",
     "mcstereo", "McCnnStereo", "McCnnStereoParams", "mc_aggregate", "mc_disparity",
     "McCnnCrossParams", "mc_cross_arms", "mc_cross_aggregate",
 ]

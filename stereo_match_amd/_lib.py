@@ -269,6 +269,25 @@ _SIGS = {
                                           _c.c_int, _c.c_size_t, _c.c_int, _c.c_int, _c.c_size_t, _c.c_void_p]),
     "sm_mccnn_join_host": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
                                       _c.c_void_p]),
+    "sm_mcacc_set_weights": (_c.c_int, [_c.c_void_p, _c.c_int, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_void_p), _c.c_int,
+                                        _c.c_int, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_void_p)]),
+    "sm_mcacc_features_device": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_size_t, _c.c_int, _c.c_int,
+                                            _c.c_size_t, _c.c_void_p]),
+    "sm_mcacc_join_device": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
+                                        _c.c_int, _c.c_int, _c.c_int, _c.c_void_p]),
+    "sm_mcacc_volume_device": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_size_t, _c.c_int,
+                                          _c.c_int, _c.c_size_t, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p]),
+    "sm_mcacc_features": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p]),
+    "sm_mcacc_join": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
+                                 _c.c_int, _c.c_int, _c.c_int, _c.c_void_p]),
+    "sm_mcacc_volume": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
+                                   _c.c_int, _c.c_int, _c.c_int, _c.c_void_p]),
+    "sm_mcacc_features_host": (_c.c_int, [_c.c_int, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_void_p), _c.c_void_p,
+                                          _c.c_int, _c.c_size_t, _c.c_int, _c.c_int, _c.c_size_t, _c.c_void_p]),
+    "sm_mcacc_join_host": (_c.c_int, [_c.c_int, _c.c_int, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_void_p), _c.c_void_p,
+                                      _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
+                                      _c.c_void_p]),
+    "sm_mcacc_sigmoid_host": (_c.c_int, [_c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "sm_mcsgm_default_params": (_c.c_int, [_c.POINTER(SmMcsgmParams)]),
     "sm_mcsgm_aggregate_device": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_size_t,
                                              _c.c_int, _c.c_int, _c.c_size_t, _c.c_int, _c.c_int,
@@ -499,6 +518,40 @@ def mccnn_join_host(fa: np.ndarray, fb: np.ndarray, D: int, min_disparity: int) 
     if rc != SM_OK:
         _raise(rc, None)
     return vol
+
+
+def mcacc_features_host(weights, biases, gray: np.ndarray, image_stride: int, row_stride: int, n: int, H: int, W: int):
+    """sm_mcacc_features_host: the CPU twin's feature maps [n, H, W, 112] of n gray images inside
+    ``gray`` (a uint8 array; images / rows ``image_stride`` / ``row_stride`` bytes apart)."""
+    feat = np.empty((n, H, W, 112), np.float32)
+    rc = load().sm_mcacc_features_host(len(weights), _ptr_array(weights), _ptr_array(biases), gray.ctypes.data, n,
+                                       image_stride, H, W, row_stride, feat.ctypes.data)
+    if rc != SM_OK:
+        _raise(rc, None)
+    return feat
+
+
+def mcacc_join_host(fc_w, fc_b, fa: np.ndarray, fb: np.ndarray, D: int, min_disparity: int, a_is_left: bool,
+                    raw: bool) -> np.ndarray:
+    """sm_mcacc_join_host: the CPU twin's volume [n, D, H, W] of feature maps [n, H, W, 112]."""
+    n, H, W = fa.shape[:3]
+    vol = np.empty((n, D, H, W), np.float32)
+    rc = load().sm_mcacc_join_host(len(fc_w) - 1, fc_w[0].shape[0], _ptr_array(fc_w), _ptr_array(fc_b), fa.ctypes.data,
+                                   fb.ctypes.data, n, H, W, D, min_disparity, int(bool(a_is_left)), int(bool(raw)),
+                                   vol.ctypes.data)
+    if rc != SM_OK:
+        _raise(rc, None)
+    return vol
+
+
+def mcacc_sigmoid_host(z: np.ndarray) -> np.ndarray:
+    """sm_mcacc_sigmoid_host: the scorer's sigmoid of a contiguous float32 array."""
+    z = np.ascontiguousarray(z, np.float32)
+    s = np.empty_like(z)
+    rc = load().sm_mcacc_sigmoid_host(z.ctypes.data, z.size, s.ctypes.data)
+    if rc != SM_OK:
+        _raise(rc, None)
+    return s
 
 
 def mcsgm_stage_arrays(n: int, H: int, W: int):
@@ -1019,6 +1072,48 @@ class Engine:
                                               vol.ctypes.data))
         return vol
 
+    def mcacc_set_weights(self, conv_w, conv_b, fc_w, fc_b):
+        """sm_mcacc_set_weights: float32 arrays w0 [112,1,3,3], w1.. [112,112,3,3], b [112]; fw0 [U,224],
+        fw1.. [U,U], the last [1,U]; fb [U], the last [1]."""
+        self._check(self._lib.sm_mcacc_set_weights(self.ctx, len(conv_w), _ptr_array(conv_w), _ptr_array(conv_b),
+                                                   len(fc_w) - 1, fc_w[0].shape[0], _ptr_array(fc_w), _ptr_array(fc_b)))
+
+    def mcacc_features(self, gray: np.ndarray) -> np.ndarray:
+        """sm_mcacc_features: contiguous uint8 [n, H, W] -> float32 [n, H, W, 112]."""
+        n, H, W = gray.shape
+        feat = np.empty((n, H, W, 112), np.float32)
+        self._check(self._lib.sm_mcacc_features(self.ctx, gray.ctypes.data, n, H, W, feat.ctypes.data))
+        return feat
+
+    def mcacc_join(self, fa: np.ndarray, fb: np.ndarray, D: int, min_disparity: int, a_is_left: bool, raw: bool) -> np.ndarray:
+        """sm_mcacc_join: feature maps [n, H, W, 112] -> the volume [n, D, H, W]."""
+        n, H, W = fa.shape[:3]
+        vol = np.empty((n, D, H, W), np.float32)
+        self._check(self._lib.sm_mcacc_join(self.ctx, fa.ctypes.data, fb.ctypes.data, n, H, W, D, min_disparity,
+                                            int(bool(a_is_left)), int(bool(raw)), vol.ctypes.data))
+        return vol
+
+    def mcacc_volume(self, a: np.ndarray, b: np.ndarray, D: int, min_disparity: int, a_is_left: bool, raw: bool) -> np.ndarray:
+        """sm_mcacc_volume: contiguous uint8 [n, H, W] images -> the volume [n, D, H, W]."""
+        n, H, W = a.shape
+        vol = np.empty((n, D, H, W), np.float32)
+        self._check(self._lib.sm_mcacc_volume(self.ctx, a.ctypes.data, b.ctypes.data, n, H, W, D, min_disparity,
+                                              int(bool(a_is_left)), int(bool(raw)), vol.ctypes.data))
+        return vol
+
+    def mcacc_features_device(self, d_gray: int, n: int, image_stride: int, H: int, W: int, row_stride: int, d_feat: int):
+        self._check(self._lib.sm_mcacc_features_device(self.ctx, d_gray, n, image_stride, H, W, row_stride, d_feat))
+
+    def mcacc_join_device(self, d_fa: int, d_fb: int, n: int, H: int, W: int, D: int, min_disparity: int, a_is_left: bool,
+                          raw: bool, d_vol: int):
+        self._check(self._lib.sm_mcacc_join_device(self.ctx, d_fa, d_fb, n, H, W, D, min_disparity, int(bool(a_is_left)),
+                                                   int(bool(raw)), d_vol))
+
+    def mcacc_volume_device(self, d_a: int, d_b: int, n: int, image_stride: int, H: int, W: int, row_stride: int,
+                            D: int, min_disparity: int, a_is_left: bool, raw: bool, d_vol: int):
+        self._check(self._lib.sm_mcacc_volume_device(self.ctx, d_a, d_b, n, image_stride, H, W, row_stride, D,
+                                                     min_disparity, int(bool(a_is_left)), int(bool(raw)), d_vol))
+
     def mccnn_features_device(self, d_gray: int, n: int, image_stride: int, H: int, W: int, row_stride: int, d_feat: int):
         self._check(self._lib.sm_mccnn_features_device(self.ctx, d_gray, n, image_stride, H, W, row_stride, d_feat))
 
@@ -1296,6 +1391,7 @@ class Engine:
     TUNE_EW_START = 15
     TUNE_EW_PATCH = 16
     TUNE_HOP_EPOCH = 17
+    TUNE_MCACC_CHUNK = 18
 
     def set_tuning(self, key: int, value: int):
         """Launch-shape knob (include/stereo_match_amd.h sm_set_tuning); 0 = automatic."""

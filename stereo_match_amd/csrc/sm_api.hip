@@ -3247,6 +3247,10 @@ int sm_set_tuning(sm_ctx* ctx, int key, int value)
         if (value < -1 || value > 1) return fail(ctx, SM_E_ARG, "PLY staging %d: -1, 0 or 1", value);
         ctx->tune_ply_stage = value;
         break;
+    case SM_TUNE_MCACC_CHUNK:
+        if (value < 0 || value > (1 << 22)) return fail(ctx, SM_E_ARG, "accurate MC-CNN cells per pass %d: 0..2^22", value);
+        ctx->tune_mcacc_chunk = value;
+        break;
     case SM_TUNE_HOP_EPOCH:  // tests: the boundary granules' 16-bit tag, to reach its wrap
         if (value < 0 || value > 0xFFFF) return fail(ctx, SM_E_ARG, "hop epoch %d: 0..65535", value);
         if (value > 0) ctx->hop_epoch = (uint32_t)value;

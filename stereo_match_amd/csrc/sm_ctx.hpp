@@ -1,6 +1,6 @@
 // sm_ctx.hpp — the host-side context of the C-ABI, shared by its translation units
 // (sm_api.hip: the matcher core; sm_api_image.hip, sm_api_cloud.hip, sm_api_png.hip,
-// sm_api_jpeg.hip, sm_api_mccnn.hip, sm_api_mcsgm.hip, sm_api_mccbca.hip: the leaf subsystems).  Host code only: every kernel header is compiled
+// sm_api_jpeg.hip, sm_api_mccnn.hip, sm_api_mcacc.hip, sm_api_mcsgm.hip, sm_api_mccbca.hip: the leaf subsystems).  Host code only: every kernel header is compiled
 // in exactly one unit (sm_paths.hpp, all templates, also in sm_deep.hip's), so none is included here.  fail, ensure, get_event, stage_in,
 // stage_out and check_sweep_errors are defined once, in sm_api.hip.
 #pragma once
@@ -91,6 +91,16 @@ struct sm_ctx {
         std::vector<float> tab_host;
         int L = 0;
     } mccnn;
+    // MC-CNN accurate matching cost (sm_mcacc.hpp): the packed convolutions, their biases and the
+    // packed scorer; sums, tables and ping-pong maps as above; the two projection maps of one image
+    // pair and the scorer's two scratch buffers of one chunk of cells; feature maps of the volume
+    // entry points; images, features and volume of the host-pointer calls
+    struct {
+        DevBuf w, b, fc, sums, tab, ping, pong, fa, fb, pa, pb, scr[2], in_a, in_b, vol;
+        std::vector<unsigned long long> sums_host;
+        std::vector<float> tab_host;
+        int L = 0, F = 0, U = 0;
+    } mcacc;
     // MC-CNN's stereo method (sm_mcsgm.hpp): the images' sums and grey-level tables (and their host
     // copies, which outlive the transfers), the normalised images, the vertical paths, the volume
     // between two iterations, the bilateral weights (cached for sigma_bits); the stage maps a
@@ -157,6 +167,7 @@ struct sm_ctx {
     int tune_bands = 0, tune_band_warmup = 0, tune_band_guess = 0;  // MODE 3 row bands (SM_TUNE_BANDS ...)
     int tune_cost_wgs = 0;  // k_sgbm_cost2 workgroups a launch aims for (SM_TUNE_COST_WGS; 0: SGBM_COST2_WGS)
     int tune_ply_stage = 0;  // SM_TUNE_PLY_STAGE: 0 / 1 the PLY rows staged in LDS, -1 written directly
+    int tune_mcacc_chunk = 0;  // SM_TUNE_MCACC_CHUNK: 0 automatic, else the cells per pass of the scorer
     int tune_sweep_xcd = 0;  // SM_TUNE_SWEEP_XCD: 1 the XCD-aware strip placement, -1 / 0 off
     long long line_groups = 0;  // launch groups run with the in-sweep E/W lines (SM_COUNTER_LINE_GROUPS)
     long long band_groups = 0;  // of them, with row bands (SM_COUNTER_BAND_GROUPS)

@@ -1,5 +1,6 @@
 """MC-CNN's stereo method after the matching cost: cross-based cost
-aggregation (optional), semi-global matching on the float32 volume of :class:`McCnnFast` with
+aggregation (optional), semi-global matching on the float32 volume of :class:`McCnnFast` or
+:class:`McCnnAccurate` with
 penalties that follow the intensity steps of both images, left-right interpolation, the sub-pixel
 step, a 5x5 median and a bilateral filter -- what turns the network's output into the ``left.png``
 / ``right.png`` that ``mapTo3D_mc_cnn.py:70-77`` reads.
@@ -20,6 +21,7 @@ import math
 import numpy as np
 
 from . import _lib
+from .mcaccurate import McCnnAccurate
 from .mccnn import MAX_DISPARITIES, McCnnFast, _is_torch_cuda
 
 MAX_OFFSET = 1 << 23
@@ -309,17 +311,18 @@ def _check_offset_range(m, D):
 
 
 class McCnnStereo:
-    """``McCnnStereo(net, params, cross).compute(left, right, numDisparities, minDisparity=0)``: the
-    features once, the volumes of both views, both aggregations, the disparity.  ``cross`` (a
+    """``McCnnStereo(net, params, cross).compute(left, right, numDisparities, minDisparity=0)``
+    (``net`` a :class:`McCnnFast` or a :class:`McCnnAccurate`): the features once, the volumes of
+    both views, both aggregations, the disparity.  ``cross`` (a
     :class:`McCnnCrossParams`; None: none) adds the cross-based cost aggregation to both views: ``i1``
     iterations before the semi-global matching and ``i2`` after it.  Returns
     ``(disp_left, disp_right_wta)``: the finished left map and the right view's winner-take-all
     disparities as float32 (what the left-right check compared against), both with invalid pixels at
     ``float(minDisparity - 1)``."""
 
-    def __init__(self, net: McCnnFast, params: McCnnStereoParams = None, cross: McCnnCrossParams = None):
-        if not isinstance(net, McCnnFast):
-            raise ValueError("net must be a McCnnFast")
+    def __init__(self, net, params: McCnnStereoParams = None, cross: McCnnCrossParams = None):
+        if not isinstance(net, (McCnnFast, McCnnAccurate)):
+            raise ValueError("net must be a McCnnFast or a McCnnAccurate")
         self.net, self.params = net, _params(params)
         self.cross = None if cross is None else _cross_params(cross)
 
@@ -343,8 +346,10 @@ class McCnnStereo:
             raise ValueError("the two images must have the same shape")
         m_r = right_min_disparity(D, m)
         fl, fr = net.features(left, host=host), net.features(right, host=host)
-        agg_l = self._aggregate(net.join(fl, fr, D, m, host=host), left, right, m, host)
-        agg_r = self._aggregate(net.join(fr, fl, D, m_r, host=host), right, left, m_r, host)
+        # the accurate net's scorer is not symmetric: its join is told the view's role
+        role_l, role_r = ({"a_is_left": True}, {"a_is_left": False}) if isinstance(net, McCnnAccurate) else ({}, {})
+        agg_l = self._aggregate(net.join(fl, fr, D, m, host=host, **role_l), left, right, m, host)
+        agg_r = self._aggregate(net.join(fr, fl, D, m_r, host=host, **role_r), right, left, m_r, host)
         disp, maps = mc_disparity(agg_l, agg_r, left, m, self.params, host=host, stages=True)
         right_wta = maps["wta_right"]
         right_wta = right_wta.float() if _is_torch_cuda(right_wta) else right_wta.astype(np.float32)
