@@ -895,6 +895,28 @@ int sm_mcacc_join_host(int F, int U, const float* const* fw, const float* const*
                        float* vol);
 int sm_mcacc_sigmoid_host(const float* z, size_t n, float* s);
 
+/* The scorer's precision, a state of the context; the default is SM_MCACC_F32, the
+ * arithmetic above.  SM_MCACC_BF16 changes only the hidden layers 1 .. F-1: both operands of every
+ * product (the previous layer's activations and the weights, rounded once at sm_mcacc_set_weights)
+ * are rounded to bfloat16 -- nearest, ties to even, subnormals kept, a finite value past bf16's
+ * largest becomes infinity, a NaN a quiet NaN with its sign: sm_mcacc_bf16_host -- and the sum
+ * of a unit is accumulated in float32 from its float32 bias.  The features, the projections, the
+ * first layer's add, the output unit (float32 on the unrounded last hidden layer), the sigmoid and
+ * the NaN border do not change.  The device runs the hidden layers on the bf16 matrix instruction
+ * in one fused kernel per image, with no scratch (SM_TUNE_MCACC_CHUNK is ignored); the order of its
+ * sums is the instruction's, so it equals sm_mcacc_join_host_bf16 (ascending k) bit for bit only
+ * where every sum is exact, and to accumulation order otherwise.  In this mode a hidden-layer
+ * weight that is not finite or rounds to infinity fails sm_mcacc_set_weights (precision set first)
+ * or the join (set later) with SM_E_ARG.  sm_mcacc_join[_device] and sm_mcacc_volume[_device]
+ * follow the state; the fast net is not concerned.  An unknown value: SM_E_ARG. */
+#define SM_MCACC_F32 0
+#define SM_MCACC_BF16 1
+int sm_mcacc_set_precision(sm_ctx* ctx, int precision);
+int sm_mcacc_join_host_bf16(int F, int U, const float* const* fw, const float* const* fb, const float* feat_a,
+                            const float* feat_b, int n, int H, int W, int D, int min_disparity, int a_is_left, int raw,
+                            float* vol);
+int sm_mcacc_bf16_host(const float* x, size_t n, uint16_t* out);
+
 /* ---- MC-CNN's stereo method after the matching cost: the paper's semi-global
  * matching on the float32 volume, left-right interpolation, sub-pixel step, 5x5 median and
  * bilateral filter.  Section 4 of the paper restated; parity with mc-cnn's code is unpinned.

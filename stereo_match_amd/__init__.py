@@ -25,7 +25,9 @@ Public surface (mirrors the reference / OpenCV names the reference uses):
 * :class:`McCnnFast` — the mc-cnn *fast* matching cost, images to the float32 cost volume of
   :meth:`StereoSGBM.computeFromCost` (``mc_cnn/script.py:9``, ``mapTo3D_mc_cnn.py:71``)
 * :class:`McCnnAccurate` — the mc-cnn *accurate* matching cost (112-map features, a fully connected
-  scorer and a sigmoid; ``mc_cnn/script.py:10``), the same volume for :class:`McCnnStereo`
+  scorer and a sigmoid; ``mc_cnn/script.py:10``), the same volume for :class:`McCnnStereo`;
+  ``precision="bf16"`` / ``with_precision("bf16")`` runs the scorer's hidden layers on the bfloat16
+  matrix instruction in one fused kernel (opt-in; the default ``"f32"`` is unchanged)
 * :class:`McCnnStereo`, :func:`mc_aggregate`, :func:`mc_disparity`, :class:`McCnnStereoParams` — mc-cnn's
   own stereo method on that volume: its SGM, left-right interpolation, sub-pixel step, median and
   bilateral filter, up to the disparity maps ``mapTo3D_mc_cnn.py:70-77`` reads;

@@ -288,6 +288,11 @@ _SIGS = {
                                       _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
                                       _c.c_void_p]),
     "sm_mcacc_sigmoid_host": (_c.c_int, [_c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "sm_mcacc_set_precision": (_c.c_int, [_c.c_void_p, _c.c_int]),
+    "sm_mcacc_join_host_bf16": (_c.c_int, [_c.c_int, _c.c_int, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_void_p),
+                                           _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
+                                           _c.c_int, _c.c_int, _c.c_void_p]),
+    "sm_mcacc_bf16_host": (_c.c_int, [_c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "sm_mcsgm_default_params": (_c.c_int, [_c.POINTER(SmMcsgmParams)]),
     "sm_mcsgm_aggregate_device": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_size_t,
                                              _c.c_int, _c.c_int, _c.c_size_t, _c.c_int, _c.c_int,
@@ -531,17 +536,33 @@ def mcacc_features_host(weights, biases, gray: np.ndarray, image_stride: int, ro
     return feat
 
 
+SM_MCACC_F32, SM_MCACC_BF16 = 0, 1
+MCACC_PRECISIONS = {"f32": SM_MCACC_F32, "bf16": SM_MCACC_BF16}
+
+
 def mcacc_join_host(fc_w, fc_b, fa: np.ndarray, fb: np.ndarray, D: int, min_disparity: int, a_is_left: bool,
-                    raw: bool) -> np.ndarray:
-    """sm_mcacc_join_host: the CPU twin's volume [n, D, H, W] of feature maps [n, H, W, 112]."""
+                    raw: bool, precision: str = "f32") -> np.ndarray:
+    """sm_mcacc_join_host (``precision="bf16"``: sm_mcacc_join_host_bf16): the CPU twin's volume
+    [n, D, H, W] of feature maps [n, H, W, 112]."""
     n, H, W = fa.shape[:3]
     vol = np.empty((n, D, H, W), np.float32)
-    rc = load().sm_mcacc_join_host(len(fc_w) - 1, fc_w[0].shape[0], _ptr_array(fc_w), _ptr_array(fc_b), fa.ctypes.data,
-                                   fb.ctypes.data, n, H, W, D, min_disparity, int(bool(a_is_left)), int(bool(raw)),
-                                   vol.ctypes.data)
+    fn = load().sm_mcacc_join_host_bf16 if MCACC_PRECISIONS[precision] == SM_MCACC_BF16 else load().sm_mcacc_join_host
+    rc = fn(len(fc_w) - 1, fc_w[0].shape[0], _ptr_array(fc_w), _ptr_array(fc_b), fa.ctypes.data, fb.ctypes.data, n, H, W,
+            D, min_disparity, int(bool(a_is_left)), int(bool(raw)), vol.ctypes.data)
     if rc != SM_OK:
         _raise(rc, None)
     return vol
+
+
+def mcacc_bf16_host(x: np.ndarray) -> np.ndarray:
+    """sm_mcacc_bf16_host: the bfloat16 bit patterns (uint16) of a float32 array, the rounding of
+    ``precision="bf16"``."""
+    x = np.ascontiguousarray(x, np.float32)
+    out = np.empty(x.shape, np.uint16)
+    rc = load().sm_mcacc_bf16_host(x.ctypes.data, x.size, out.ctypes.data)
+    if rc != SM_OK:
+        _raise(rc, None)
+    return out
 
 
 def mcacc_sigmoid_host(z: np.ndarray) -> np.ndarray:
@@ -1077,6 +1098,12 @@ class Engine:
         fw1.. [U,U], the last [1,U]; fb [U], the last [1]."""
         self._check(self._lib.sm_mcacc_set_weights(self.ctx, len(conv_w), _ptr_array(conv_w), _ptr_array(conv_b),
                                                    len(fc_w) - 1, fc_w[0].shape[0], _ptr_array(fc_w), _ptr_array(fc_b)))
+
+    def mcacc_set_precision(self, precision: str):
+        """sm_mcacc_set_precision: "f32" or "bf16", for the joins and volumes that follow."""
+        if precision not in MCACC_PRECISIONS:
+            raise ValueError(f"precision {precision!r}: 'f32' or 'bf16'")
+        self._check(self._lib.sm_mcacc_set_precision(self.ctx, MCACC_PRECISIONS[precision]))
 
     def mcacc_features(self, gray: np.ndarray) -> np.ndarray:
         """sm_mcacc_features: contiguous uint8 [n, H, W] -> float32 [n, H, W, 112]."""

@@ -73,7 +73,39 @@ int mcacc_dense(sm_ctx* ctx, const float* in, const float* wt, const float* bias
     return SM_OK;
 }
 
+// precision "bf16": one launch per image, no scratch
+void mcacc_launch_fused16(sm_ctx* ctx, const smk::AcFusedArgs& fa, int U)
+{
+    const unsigned xt = ((unsigned)fa.W + smk::AC_GX - 1) / smk::AC_GX, ndg = ((unsigned)fa.D + smk::AC_GD - 1) / smk::AC_GD;
+    const dim3 grid(xt * ndg, (unsigned)std::min(fa.H, 65535));
+    switch (U / 32) {
+    case 1: hipLaunchKernelGGL(smk::k_ac_fused16<1>, grid, dim3(smk::AC_BLOCK), 0, ctx->stream, fa); break;
+    case 2: hipLaunchKernelGGL(smk::k_ac_fused16<2>, grid, dim3(smk::AC_BLOCK), 0, ctx->stream, fa); break;
+    case 3: hipLaunchKernelGGL(smk::k_ac_fused16<3>, grid, dim3(smk::AC_BLOCK), 0, ctx->stream, fa); break;
+    case 4: hipLaunchKernelGGL(smk::k_ac_fused16<4>, grid, dim3(smk::AC_BLOCK), 0, ctx->stream, fa); break;
+    case 5: hipLaunchKernelGGL(smk::k_ac_fused16<5>, grid, dim3(smk::AC_BLOCK), 0, ctx->stream, fa); break;
+    case 6: hipLaunchKernelGGL(smk::k_ac_fused16<6>, grid, dim3(smk::AC_BLOCK), 0, ctx->stream, fa); break;
+    case 7: hipLaunchKernelGGL(smk::k_ac_fused16<7>, grid, dim3(smk::AC_BLOCK), 0, ctx->stream, fa); break;
+    case 8: hipLaunchKernelGGL(smk::k_ac_fused16<8>, grid, dim3(smk::AC_BLOCK), 0, ctx->stream, fa); break;
+    case 9: hipLaunchKernelGGL(smk::k_ac_fused16<9>, grid, dim3(smk::AC_BLOCK), 0, ctx->stream, fa); break;
+    case 10: hipLaunchKernelGGL(smk::k_ac_fused16<10>, grid, dim3(smk::AC_BLOCK), 0, ctx->stream, fa); break;
+    case 11: hipLaunchKernelGGL(smk::k_ac_fused16<11>, grid, dim3(smk::AC_BLOCK), 0, ctx->stream, fa); break;
+    default: hipLaunchKernelGGL(smk::k_ac_fused16<12>, grid, dim3(smk::AC_BLOCK), 0, ctx->stream, fa); break;
+    }
+}
+
+const char* const MCACC_BF16_BAD = "mcacc: a weight of hidden layer %d is not finite or overflows in bf16";
+
 }  // namespace
+
+int sm_mcacc_set_precision(sm_ctx* ctx, int precision)
+{
+    if (!ctx) return fail(nullptr, SM_E_ARG, "ctx is NULL");
+    if (precision != SM_MCACC_F32 && precision != SM_MCACC_BF16)
+        return fail(ctx, SM_E_ARG, "mcacc: precision %d (SM_MCACC_F32 or SM_MCACC_BF16)", precision);
+    ctx->mcacc.precision = precision;
+    return SM_OK;
+}
 
 int sm_mcacc_set_weights(sm_ctx* ctx, int L, const float* const* w, const float* const* b, int F, int U,
                          const float* const* fw, const float* const* fb)
@@ -87,15 +119,21 @@ int sm_mcacc_set_weights(sm_ctx* ctx, int L, const float* const* w, const float*
     std::vector<float> wp(smk::ac_pack_conv_floats(L)), bp((size_t)L * smk::AC_CP), fp(fc.floats());
     smk::ac_pack_conv(L, w, b, wp.data(), bp.data());
     smk::ac_pack_fc(fc, fw, fb, fp.data());
+    // the hidden matrices in bf16, rounded here once; a net bf16 cannot hold stays usable in f32
+    const int bad = smk::ac_fc_bf16_bad(F, U, fw);
+    if (bad && ctx->mcacc.precision == SM_MCACC_BF16) return fail(ctx, SM_E_ARG, MCACC_BF16_BAD, bad);
+    std::vector<uint16_t> qp(std::max<size_t>(smk::ac_pack_fc_bf16_count(F, U), 8));
+    if (!bad) smk::ac_pack_fc_bf16(F, U, fw, qp.data());
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // no queued layer still reads the old weights
     ctx->mcacc.L = 0;
     if ((rc = stage_in(ctx, {{ctx->mcacc.w, wp.data(), wp.size() * sizeof(float)},
                              {ctx->mcacc.b, bp.data(), bp.size() * sizeof(float)},
-                             {ctx->mcacc.fc, fp.data(), fp.size() * sizeof(float)}})) != SM_OK)
+                             {ctx->mcacc.fc, fp.data(), fp.size() * sizeof(float)},
+                             {ctx->mcacc.fc16, qp.data(), qp.size() * sizeof(uint16_t)}})) != SM_OK)
         return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // the packed arrays live on this frame
-    ctx->mcacc.L = L, ctx->mcacc.F = F, ctx->mcacc.U = U;
+    ctx->mcacc.L = L, ctx->mcacc.F = F, ctx->mcacc.U = U, ctx->mcacc.bf16_bad = bad;
     return SM_OK;
 }
 
@@ -176,13 +214,17 @@ int sm_mcacc_join_device(sm_ctx* ctx, const float* d_feat_a, const float* d_feat
     const int F = fc.F, U = fc.U;
     const unsigned npix = (unsigned)H * (unsigned)W;
     const size_t cells = (size_t)D * npix, pbytes = (size_t)npix * U * sizeof(float);
+    const bool bf16 = mc.precision == SM_MCACC_BF16;
+    if (bf16 && mc.bf16_bad) return fail(ctx, SM_E_ARG, MCACC_BF16_BAD, mc.bf16_bad);
     if ((rc = ensure(ctx, mc.pa, pbytes)) != SM_OK) return rc;
     if ((rc = ensure(ctx, mc.pb, pbytes)) != SM_OK) return rc;
 
     // cells per pass: the scratch (one buffer, two with a U x U layer) takes at most a quarter of
     // what is free, counting what the context already holds for it; never sized from H W D
+    // (precision "bf16" has no scratch and no chunks: one fused kernel per image)
     size_t chunk = (size_t)ctx->tune_mcacc_chunk;
     const int nscr = F > 1 ? 2 : 1;
+    if (bf16) chunk = cells;
     if (!chunk) {
         size_t free_b = 0, total_b = 0;
         HIP_TRY(ctx, hipMemGetInfo(&free_b, &total_b));
@@ -192,7 +234,7 @@ int sm_mcacc_join_device(sm_ctx* ctx, const float* d_feat_a, const float* d_feat
         if (!chunk) return fail(ctx, SM_E_HIP, "mcacc: not enough free device memory for the scorer's scratch");
     }
     chunk = std::min(chunk, cells);
-    for (int i = 0; i < nscr; i++)
+    for (int i = 0; i < nscr && !bf16; i++)
         if ((rc = ensure(ctx, mc.scr[i], chunk * U * sizeof(float))) != SM_OK) return rc;
 
     const float* fcp = (const float*)mc.fc.p;
@@ -206,6 +248,12 @@ int sm_mcacc_join_device(sm_ctx* ctx, const float* d_feat_a, const float* d_feat
                         npix, smk::AC_C, U, false);
         }
         float* vol = d_vol + (size_t)img * cells;
+        if (bf16) {
+            smk::AcFusedArgs ua{proj[0], proj[1], (const uint16_t*)mc.fc16.p, fcp + fc.bias(0), fcp + fc.last(),
+                                fcp + fc.bias(F), vol, H, W, D, F, m, raw != 0};
+            mcacc_launch_fused16(ctx, ua, U);
+            continue;
+        }
         for (size_t c0 = 0; c0 < cells; c0 += chunk) {
             const unsigned nc = (unsigned)std::min(chunk, cells - c0);
             smk::AcCellArgs ha{proj[0], proj[1], (float*)mc.scr[0].p, c0, nc, H, W, U, m};
@@ -324,6 +372,33 @@ int sm_mcacc_join_host(int F, int U, const float* const* fw, const float* const*
     std::vector<float> fp(fc.floats());
     smk::ac_pack_fc(fc, fw, fb, fp.data());
     smk::mcacc_join_host(fc, fp.data(), feat_a, feat_b, n, H, W, D, min_disparity, a_is_left != 0, raw != 0, vol);
+    return SM_OK;
+}
+
+int sm_mcacc_join_host_bf16(int F, int U, const float* const* fw, const float* const* fb, const float* feat_a,
+                            const float* feat_b, int n, int H, int W, int D, int min_disparity, int a_is_left, int raw,
+                            float* vol)
+{
+    int rc;
+    if ((rc = mcacc_check_fc(nullptr, F, U, fw, fb)) != SM_OK) return rc;
+    if (!feat_a || !feat_b || !vol) return fail(nullptr, SM_E_ARG, "mcacc: a required pointer is NULL");
+    if ((rc = mcacc_check_images(nullptr, n, H, W)) != SM_OK) return rc;
+    if ((rc = mcacc_check_planes(nullptr, D)) != SM_OK) return rc;
+    const int bad = smk::ac_fc_bf16_bad(F, U, fw);
+    if (bad) return fail(nullptr, SM_E_ARG, MCACC_BF16_BAD, bad);
+    smk::AcFc fc;
+    fc.F = F, fc.U = U;
+    std::vector<float> fp(fc.floats());
+    smk::ac_pack_fc(fc, fw, fb, fp.data());
+    smk::ac_round_fc(fc, fp.data());
+    smk::mcacc_join_host(fc, fp.data(), feat_a, feat_b, n, H, W, D, min_disparity, a_is_left != 0, raw != 0, vol, true);
+    return SM_OK;
+}
+
+int sm_mcacc_bf16_host(const float* x, size_t n, uint16_t* out)
+{
+    if (!x || !out) return fail(nullptr, SM_E_ARG, "mcacc: a required pointer is NULL");
+    for (size_t i = 0; i < n; i++) out[i] = smk::ac_bf16(x[i]);
     return SM_OK;
 }
 

@@ -94,12 +94,15 @@ struct sm_ctx {
     // MC-CNN accurate matching cost (sm_mcacc.hpp): the packed convolutions, their biases and the
     // packed scorer; sums, tables and ping-pong maps as above; the two projection maps of one image
     // pair and the scorer's two scratch buffers of one chunk of cells; feature maps of the volume
-    // entry points; images, features and volume of the host-pointer calls
+    // entry points; images, features and volume of the host-pointer calls; the hidden matrices in
+    // bf16 (fc16), the scorer's precision (SM_MCACC_*) and the first hidden layer whose weights
+    // bf16 cannot hold (0: none)
     struct {
-        DevBuf w, b, fc, sums, tab, ping, pong, fa, fb, pa, pb, scr[2], in_a, in_b, vol;
+        DevBuf w, b, fc, fc16, sums, tab, ping, pong, fa, fb, pa, pb, scr[2], in_a, in_b, vol;
         std::vector<unsigned long long> sums_host;
         std::vector<float> tab_host;
         int L = 0, F = 0, U = 0;
+        int precision = 0, bf16_bad = 0;
     } mcacc;
     // MC-CNN's stereo method (sm_mcsgm.hpp): the images' sums and grey-level tables (and their host
     // copies, which outlive the transfers), the normalised images, the vertical paths, the volume

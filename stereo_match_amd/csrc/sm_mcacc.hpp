@@ -127,6 +127,74 @@ __host__ __device__ inline float ac_sigmoid(float z)
     return 1.0f / __builtin_fmaf(e, 1.0f, 1.0f);
 }
 
+// ---- precision "bf16" (DESIGN.md §4.21): only the scorer's hidden layers 1 .. F-1 change.
+//   ac_bf16(x)  the upper 16 bits of x rounded to nearest, ties to even; subnormals the same way (no
+//               flush); +-inf kept; a finite value past bf16's largest becomes +-inf; a NaN becomes
+//               a quiet NaN with its sign.  bf(x) = ac_bf16_float(ac_bf16(x)).
+//   h1          as above, in f32 (the feature net and the projections PL / PR do not change).
+//   h_i[u]      relu(fb_i[u] + sum over k of bf(h_{i-1}[k]) * bf(fw_i[u][k])), i = 1 .. F-1: every
+//               product is exact in f32, the sum is accumulated in f32 from the f32 bias, h_i stays
+//               f32 until it is rounded as the next layer's operand.  Twin: the f32 additions in
+//               ascending k.  Device: the order and internal rounding of v_mfma_f32_32x32x16_bf16,
+//               which are not documented -- the one place where the two may differ.
+//   z           f32 arithmetic on the unrounded h_{F-1} and the f32 fw_F from fb_F: the twin an
+//               ascending fmaf chain, the device any order.  Sigmoid, sign, NaN border, raw,
+//               a_is_left and the layout as above.  F = 1 has no hidden layer and follows the same
+//               rules.
+//   weights     the hidden layers' are rounded once; one that is not finite or rounds to +-inf is an
+//               error in this mode.
+// Integer operands with |fb| + sum |terms| < 2^24 make every sum exact in any order: device ==
+// twin, bit for bit.
+__host__ __device__ inline uint16_t ac_bf16(float x)
+{
+    uint32_t b;
+    __builtin_memcpy(&b, &x, 4);
+    if ((b & 0x7FFFFFFFu) > 0x7F800000u) return (uint16_t)((b >> 16) | 0x0040u);
+    return (uint16_t)((b + 0x7FFFu + ((b >> 16) & 1u)) >> 16);
+}
+
+__host__ __device__ inline float ac_bf16_float(uint16_t v)
+{
+    const uint32_t b = (uint32_t)v << 16;
+    float f;
+    __builtin_memcpy(&f, &b, 4);
+    return f;
+}
+
+// the first hidden layer (1 .. F-1) with a weight that is not finite or rounds to +-inf, or 0
+inline int ac_fc_bf16_bad(int F, int U, const float* const* fw)
+{
+    for (int i = 1; i < F; i++)
+        for (size_t j = 0; j < (size_t)U * U; j++)
+            if ((ac_bf16(fw[i][j]) & 0x7F80u) == 0x7F80u) return i;
+    return 0;
+}
+
+// the packed scorer (ac_pack_fc) with its hidden matrices replaced by their bf16 values: the twin's
+inline void ac_round_fc(const AcFc& fc, float* fcp)
+{
+    for (size_t j = fc.hid(1); j < fc.last(); j++) fcp[j] = ac_bf16_float(ac_bf16(fcp[j]));
+}
+
+// The hidden matrices as the device reads them: [layer][t][q][lane][8] bf16, the A fragment of
+// mfma_f32_32x32x16_bf16 for output tile t (units 32 t ..) and k-step q.  Lane l = (r = l & 31,
+// h = l >> 5), element j: fw[32 t + r][ac_bf16_unit(q, h, j)].  The k order is the one an
+// accumulator tile implies when its registers 8 s .. 8 s + 7 become the next k-step's operand.
+constexpr int ac_bf16_unit(int q, int h, int j) { return 16 * q + 8 * (j >> 2) + 4 * h + (j & 3); }
+
+inline size_t ac_pack_fc_bf16_count(int F, int U) { return (size_t)(F - 1) * U * U; }
+
+inline void ac_pack_fc_bf16(int F, int U, const float* const* fw, uint16_t* dst)
+{
+    const int NU = U / 32, NQ = U / 16;
+    for (int i = 1; i < F; i++)
+        for (int t = 0; t < NU; t++)
+            for (int q = 0; q < NQ; q++)
+                for (int l = 0; l < 64; l++)
+                    for (int j = 0; j < 8; j++)
+                        *dst++ = ac_bf16(fw[i][(size_t)(32 * t + (l & 31)) * U + ac_bf16_unit(q, l >> 5, j)]);
+}
+
 // ---- the twin: plain loops, explicit fmaf, built for CPUs with FMA units and for any x86-64
 // (sm_mccnn.hpp).
 
@@ -218,6 +286,48 @@ __attribute__((always_inline)) inline void ac_score_body(const AcFc& fc, const f
             }
 }
 
+// precision "bf16": fcp is ac_round_fc's, so a hidden weight is its bf16 value already
+__attribute__((always_inline)) inline void ac_score16_body(const AcFc& fc, const float* fcp, const float* pa,
+                                                           const float* pb, int H, int W, int D, long long m, bool raw,
+                                                           float* vol)
+{
+    const int U = fc.U, F = fc.F;
+    float h[AC_MAXU], acc[AC_MAXU];
+    for (int d = 0; d < D; d++)
+        for (int y = 0; y < H; y++)
+            for (int x = 0; x < W; x++) {
+                const long long xb = (long long)x - (m + d);
+                float v = std::nanf("");
+                if (xb >= 0 && xb < W) {
+                    const float* a = pa + ((size_t)y * W + x) * U;
+                    const float* b = pb + ((size_t)y * W + (size_t)xb) * U;
+                    for (int u = 0; u < U; u++) {
+                        const float s = a[u] + b[u];
+                        h[u] = s > 0.0f ? s : 0.0f;
+                    }
+                    for (int i = 1; i < F; i++) {
+                        const float* wt = fcp + fc.hid(i);
+                        const float* bi = fcp + fc.bias(i);
+                        for (int u = 0; u < U; u++) acc[u] = bi[u];
+                        for (int k = 0; k < U; k++) {
+                            const float hv = ac_bf16_float(ac_bf16(h[k]));
+                            const float* wr = wt + (size_t)k * U;
+                            for (int u = 0; u < U; u++) {
+                                const float p = hv * wr[u];  // exact; no contraction in this header
+                                acc[u] = acc[u] + p;
+                            }
+                        }
+                        for (int u = 0; u < U; u++) h[u] = acc[u] > 0.0f ? acc[u] : 0.0f;
+                    }
+                    const float* wl = fcp + fc.last();
+                    float z = fcp[fc.bias(F)];
+                    for (int k = 0; k < U; k++) z = __builtin_fmaf(h[k], wl[k], z);
+                    v = raw ? -z : -ac_sigmoid(z);
+                }
+                vol[((size_t)d * H + y) * W + x] = v;
+            }
+}
+
 SM_MC_FMA_TARGET inline void ac_features_image_fma(int L, const float* wp, const float* bias, const float* plane, int H,
                                                    int W, float* ping, float* pong, float* feat)
 {
@@ -246,6 +356,17 @@ inline void ac_score_any(const AcFc& fc, const float* fcp, const float* pa, cons
                          long long m, bool raw, float* vol)
 {
     ac_score_body(fc, fcp, pa, pb, H, W, D, m, raw, vol);
+}
+
+SM_MC_FMA_TARGET inline void ac_score16_fma(const AcFc& fc, const float* fcp, const float* pa, const float* pb, int H,
+                                            int W, int D, long long m, bool raw, float* vol)
+{
+    ac_score16_body(fc, fcp, pa, pb, H, W, D, m, raw, vol);
+}
+inline void ac_score16_any(const AcFc& fc, const float* fcp, const float* pa, const float* pb, int H, int W, int D,
+                           long long m, bool raw, float* vol)
+{
+    ac_score16_body(fc, fcp, pa, pb, H, W, D, m, raw, vol);
 }
 
 // features of n images (rows row_stride, images image_stride bytes apart) into feat [n][H][W][112];
@@ -278,8 +399,9 @@ inline int mcacc_features_host(int L, const float* wp, const float* bias, const 
 }
 
 // the volume [n][D][H][W] of feature maps [n][H][W][112]; a_is_left: fa feeds PL (and fb PR)
+// bf16: fcp is ac_round_fc's and the cells follow precision "bf16"
 inline void mcacc_join_host(const AcFc& fc, const float* fcp, const float* fa, const float* fb, int n, int H, int W,
-                            int D, int minD, bool a_is_left, bool raw, float* vol)
+                            int D, int minD, bool a_is_left, bool raw, float* vol, bool bf16 = false)
 {
     const size_t npix = (size_t)H * W, fimg = npix * AC_C, vimg = (size_t)D * npix;
     const int m = mc_clamp_min_disparity(minD, W, D);
@@ -297,7 +419,11 @@ inline void mcacc_join_host(const AcFc& fc, const float* fcp, const float* fa, c
             else
                 ac_project_any(f, npix, fc.U, wt, bias, out);
         }
-        if (fma)
+        if (bf16 && fma)
+            ac_score16_fma(fc, fcp, pa.data(), pb.data(), H, W, D, m, raw, vol + img * vimg);
+        else if (bf16)
+            ac_score16_any(fc, fcp, pa.data(), pb.data(), H, W, D, m, raw, vol + img * vimg);
+        else if (fma)
             ac_score_fma(fc, fcp, pa.data(), pb.data(), H, W, D, m, raw, vol + img * vimg);
         else
             ac_score_any(fc, fcp, pa.data(), pb.data(), H, W, D, m, raw, vol + img * vimg);
@@ -616,6 +742,141 @@ __global__ __launch_bounds__(AC_BLOCK) void k_ac_final(AcFinalArgs a)
     const int x = (int)(pix % (unsigned)a.W);
     const int xb = x - (a.m + d);
     a.vol[c] = (xb >= 0 && xb < a.W) ? (a.raw ? -z : -ac_sigmoid(z)) : __builtin_nanf("");
+}
+
+// ---- precision "bf16": the whole scorer of a tile of cells in one kernel
+typedef __bf16 ac_b8 __attribute__((ext_vector_type(8)));
+
+constexpr int AC_GX = 32;  // cells of a wave: 32 consecutive columns of one row of one plane
+constexpr int AC_GD = 4;   // planes of a workgroup: wave w takes plane 4 blockIdx + w of the same columns
+
+struct AcFusedArgs {
+    const float* pa;      // [H][W][U] the projection of a's features
+    const float* pb;      // [H][W][U] of b's
+    const uint16_t* wq;   // ac_pack_fc_bf16's
+    const float* bias;    // fb_0 .. fb_{F-1}, [U] each (fb_0 is in the projection already)
+    const float* wl;      // [U] the output unit
+    const float* bl;      // its bias
+    float* vol;           // the image's volume [D][H][W]
+    int H, W, D, F, m, raw;
+};
+
+__device__ inline ac_b8 ac_pack_b8(const float* v)
+{
+    uint32_t p[4];
+    for (int j = 0; j < 4; j++) p[j] = (uint32_t)ac_bf16(v[2 * j]) | ((uint32_t)ac_bf16(v[2 * j + 1]) << 16);
+    return __builtin_bit_cast(ac_b8, make_uint4(p[0], p[1], p[2], p[3]));
+}
+
+// Transposed products on mfma_f32_32x32x16_bf16: X[unit][cell] = W[unit][k] H[k][cell], the weights
+// the A operand, the activations the B operand.  A wave owns 32 cells (the columns of X, one per
+// lane & 31) through every layer: a result tile has its units in the 16 registers, which is what the
+// next layer sums over, so registers 8 s .. 8 s + 7 of tile t, rounded, are the B fragment of k-step
+// 2 t + s with no lane movement and no LDS (the k order inside a step is ac_bf16_unit's, and the
+// packed weights follow it).  h1 is loaded in that order too.  The activations of a cell never
+// leave the registers: 2 NU fragments in, 2 NU out, two accumulator tiles; one wave per SIMD.  The
+// A fragments are 1 KB coalesced reads of the packed weights, the same sequence in every wave of
+// the chip (L2; the four waves of a workgroup run the same columns at four consecutive planes, so
+// PL is read once per workgroup and PR's rows overlap in all but three columns).  The last hidden
+// layer is not rounded: it goes straight into the output unit's partial sums, which the two lane
+// halves of a cell add at the end.
+template <int NU>
+__global__ __launch_bounds__(AC_BLOCK) void k_ac_fused16(AcFusedArgs a)
+{
+    constexpr int U = 32 * NU, NQ = 2 * NU, TT = NU % 2 == 0 ? 2 : 1;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int c = lane & 31, h = lane >> 5;
+    const int ndg = (a.D + AC_GD - 1) / AC_GD;
+    const int dg = (int)(blockIdx.x % (unsigned)ndg), xt = (int)(blockIdx.x / (unsigned)ndg);
+    const int d = AC_GD * dg + wv, x = AC_GX * xt + c;
+    if (d >= a.D) return;  // the whole wave; no barrier below
+    const int xb = x - (a.m + d);
+    const bool inx = x < a.W, ok = inx && xb >= 0 && xb < a.W;
+
+    for (int y = blockIdx.y; y < a.H; y += gridDim.y) {
+        ac_b8 hb[NQ];
+        float z = 0.0f;
+        {
+            const float* pa = a.pa + ((size_t)y * a.W + (ok ? x : 0)) * U + 4 * h;
+            const float* pb = a.pb + ((size_t)y * a.W + (ok ? xb : 0)) * U + 4 * h;
+#pragma unroll
+            for (int q = 0; q < NQ; q++) {
+                float v[8];
+#pragma unroll
+                for (int g = 0; g < 2; g++) {
+                    float4 p = make_float4(0.0f, 0.0f, 0.0f, 0.0f), r = p;
+                    if (ok) {
+                        p = *(const float4*)(pa + 16 * q + 8 * g);
+                        r = *(const float4*)(pb + 16 * q + 8 * g);
+                    }
+                    const float s0 = p.x + r.x, s1 = p.y + r.y, s2 = p.z + r.z, s3 = p.w + r.w;
+                    v[4 * g + 0] = s0 > 0.0f ? s0 : 0.0f;
+                    v[4 * g + 1] = s1 > 0.0f ? s1 : 0.0f;
+                    v[4 * g + 2] = s2 > 0.0f ? s2 : 0.0f;
+                    v[4 * g + 3] = s3 > 0.0f ? s3 : 0.0f;
+                }
+                if (a.F == 1) {
+#pragma unroll
+                    for (int g = 0; g < 2; g++) {
+                        const float4 w = *(const float4*)(a.wl + 16 * q + 8 * g + 4 * h);
+                        z = __builtin_fmaf(v[4 * g + 0], w.x, z);
+                        z = __builtin_fmaf(v[4 * g + 1], w.y, z);
+                        z = __builtin_fmaf(v[4 * g + 2], w.z, z);
+                        z = __builtin_fmaf(v[4 * g + 3], w.w, z);
+                    }
+                }
+                hb[q] = ac_pack_b8(v);
+            }
+        }
+
+        for (int i = 1; i < a.F; i++) {
+            const ac_b8* wq = (const ac_b8*)(a.wq + (size_t)(i - 1) * U * U) + lane;
+            const float* bi = a.bias + (size_t)i * U + 4 * h;
+            const bool lastl = i == a.F - 1;
+            ac_b8 hn[NQ];
+#pragma unroll
+            for (int t0 = 0; t0 < NU; t0 += TT) {
+                ac_f16 acc[TT];
+#pragma unroll
+                for (int tt = 0; tt < TT; tt++)
+#pragma unroll
+                    for (int g = 0; g < 4; g++) {
+                        const float4 b4 = *(const float4*)(bi + 32 * (t0 + tt) + 8 * g);
+                        acc[tt][4 * g + 0] = b4.x, acc[tt][4 * g + 1] = b4.y;
+                        acc[tt][4 * g + 2] = b4.z, acc[tt][4 * g + 3] = b4.w;
+                    }
+#pragma unroll
+                for (int q = 0; q < NQ; q++)
+#pragma unroll
+                    for (int tt = 0; tt < TT; tt++)
+                        acc[tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wq[((t0 + tt) * NQ + q) * 64], hb[q], acc[tt], 0, 0, 0);
+#pragma unroll
+                for (int tt = 0; tt < TT; tt++) {
+                    float v[16];
+#pragma unroll
+                    for (int r = 0; r < 16; r++) v[r] = acc[tt][r] > 0.0f ? acc[tt][r] : 0.0f;
+                    if (lastl) {
+#pragma unroll
+                        for (int g = 0; g < 4; g++) {
+                            const float4 w = *(const float4*)(a.wl + 32 * (t0 + tt) + 8 * g + 4 * h);
+                            z = __builtin_fmaf(v[4 * g + 0], w.x, z);
+                            z = __builtin_fmaf(v[4 * g + 1], w.y, z);
+                            z = __builtin_fmaf(v[4 * g + 2], w.z, z);
+                            z = __builtin_fmaf(v[4 * g + 3], w.w, z);
+                        }
+                    }
+                    hn[2 * (t0 + tt)] = ac_pack_b8(v);
+                    hn[2 * (t0 + tt) + 1] = ac_pack_b8(v + 8);
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < NQ; q++) hb[q] = hn[q];
+        }
+
+        z = (z + __shfl_xor(z, 32)) + a.bl[0];
+        if (h == 0 && inx)
+            a.vol[((size_t)d * a.H + y) * a.W + x] = ok ? (a.raw ? -z : -ac_sigmoid(z)) : __builtin_nanf("");
+    }
 }
 #endif  // __HIPCC__ && !SM_MCACC_NO_KERNELS
 

@@ -16,6 +16,15 @@ ones; a trained net comes from an ``.npz`` with the keys ``w{i}, b{i}`` (``w0`` 
 ``[112, 1, 3, 3]``, ``w1..`` ``[112, 112, 3, 3]``, ``b_i`` ``[112]``) and ``fw{i}, fb{i}``
 (``nn.Linear``'s ``[out, in]``: ``fw0`` ``[U, 224]``, ``fw1..`` ``[U, U]``, the last ``[1, U]``;
 ``fb_i`` ``[U]``, the last ``[1]``).
+
+``precision="bf16"`` runs the scorer's hidden layers 1 .. F-1 on the bfloat16
+matrix instruction: the activations entering a layer and its weights are rounded to bfloat16
+(nearest, ties to even), every unit's sum is accumulated in float32 from its float32 bias.  The
+feature net, the first layer (the two projections and their add), the output unit, the sigmoid and
+the NaN border stay float32.  The default ``"f32"`` is the arithmetic above, bit for bit.  In bf16
+mode the device and the twin agree bit for bit where every sum is exact (integer nets) and to the
+order of the float32 additions otherwise.  With no trained weights, the effect of bf16 on real
+disparities is unknown.
 """
 from __future__ import annotations
 
@@ -28,6 +37,7 @@ FEATURES = 112
 MAX_LAYERS = 6
 MAX_FC_LAYERS = 4
 MAX_UNITS = 384
+PRECISIONS = ("f32", "bf16")
 
 
 def _frozen(arr):
@@ -42,7 +52,9 @@ class McCnnAccurate:
     unit, so ``fc_w`` and ``fc_b`` hold ``F + 1`` arrays.  The arrays are copied and the copies
     (``.weights``, ``.biases``, ``.fc_weights``, ``.fc_biases``) are read-only."""
 
-    def __init__(self, conv_w, conv_b, fc_w, fc_b, device: int = 0):
+    def __init__(self, conv_w, conv_b, fc_w, fc_b, device: int = 0, precision: str = "f32"):
+        if precision not in PRECISIONS:
+            raise ValueError(f"precision {precision!r}: one of {PRECISIONS}")
         conv_w, conv_b, fc_w, fc_b = list(conv_w), list(conv_b), list(fc_w), list(fc_b)
         L, F = len(conv_w), len(fc_w) - 1
         if not 1 <= L <= MAX_LAYERS or len(conv_b) != L:
@@ -75,9 +87,34 @@ class McCnnAccurate:
             self.fc_biases.append(_frozen(b))
         self.layers, self.fc_layers, self.units = L, F, int(U)
         self.device = int(device)
+        self._root = self  # the net whose arrays these are: with_precision's copies share one upload
+        self._precision = precision
+        if precision == "bf16":
+            self._check_bf16()
+
+    @property
+    def precision(self) -> str:
+        """``"f32"`` or ``"bf16"``: the arithmetic of the scorer's hidden layers (read-only)."""
+        return self._precision
+
+    def _check_bf16(self):
+        for i in range(1, self.fc_layers):
+            if ((_lib.mcacc_bf16_host(self.fc_weights[i]) & 0x7F80) == 0x7F80).any():
+                raise ValueError(f"scorer layer {i}: a weight is not finite or overflows in bfloat16 (precision='bf16')")
+
+    def with_precision(self, precision: str):
+        """A net of the same (shared, read-only) arrays whose scorer runs in ``precision``."""
+        if precision not in PRECISIONS:
+            raise ValueError(f"precision {precision!r}: one of {PRECISIONS}")
+        other = object.__new__(type(self))
+        other.__dict__.update(self.__dict__)
+        other._precision = precision
+        if precision == "bf16":
+            other._check_bf16()
+        return other
 
     @classmethod
-    def from_npz(cls, path, device: int = 0):
+    def from_npz(cls, path, device: int = 0, precision: str = "f32"):
         """The net stored under the keys ``w{i}, b{i}, fw{i}, fb{i}`` (module docstring)."""
         with np.load(path) as z:
             L = F = 0
@@ -86,10 +123,11 @@ class McCnnAccurate:
             while f"fw{F}" in z.files:
                 F += 1
             return cls([z[f"w{i}"] for i in range(L)], [z[f"b{i}"] for i in range(L)],
-                       [z[f"fw{i}"] for i in range(F)], [z[f"fb{i}"] for i in range(F)], device)
+                       [z[f"fw{i}"] for i in range(F)], [z[f"fb{i}"] for i in range(F)], device, precision)
 
     @classmethod
-    def random(cls, conv_layers: int = 4, fc_layers: int = 4, units: int = 384, seed: int = 0, device: int = 0):
+    def random(cls, conv_layers: int = 4, fc_layers: int = 4, units: int = 384, seed: int = 0, device: int = 0,
+               precision: str = "f32"):
         """He-scaled random weights (std sqrt(2 / fan_in)), small random biases: untrained."""
         rng = np.random.default_rng(seed)
         units = int(units)
@@ -105,7 +143,7 @@ class McCnnAccurate:
             out = 1 if i == int(fc_layers) else units
             fws.append((rng.standard_normal((out, fan_in)) * np.sqrt(2.0 / fan_in)).astype(np.float32))
             fbs.append((rng.standard_normal(out) * 0.05).astype(np.float32))
-        return cls(ws, bs, fws, fbs, device)
+        return cls(ws, bs, fws, fbs, device, precision)
 
     def save_npz(self, path):
         np.savez(path, **{f"w{i}": w for i, w in enumerate(self.weights)}, **{f"b{i}": b for i, b in enumerate(self.biases)},
@@ -120,9 +158,10 @@ class McCnnAccurate:
 
     def _engine(self, device=None):
         eng = _lib.engine(self.device if device is None else device)
-        if getattr(eng, "_mcacc_model", None) is not self:
+        eng.mcacc_set_precision(self._precision)  # a state of the context: every call sets its own
+        if getattr(eng, "_mcacc_model", None) is not self._root:
             eng.mcacc_set_weights(self.weights, self.biases, self.fc_weights, self.fc_biases)
-            eng._mcacc_model = self
+            eng._mcacc_model = self._root
         return eng
 
     # ---- public
@@ -185,7 +224,7 @@ class McCnnAccurate:
             fa, fb = fa[None], fb[None]
         fa, fb = np.ascontiguousarray(fa), np.ascontiguousarray(fb)
         if host:
-            return _lib.mcacc_join_host(self.fc_weights, self.fc_biases, fa, fb, D, m, a_is_left, raw)
+            return _lib.mcacc_join_host(self.fc_weights, self.fc_biases, fa, fb, D, m, a_is_left, raw, self._precision)
         return self._engine().mcacc_join(fa, fb, D, m, a_is_left, raw)
 
     def cost_volume(self, a, b, numDisparities, minDisparity: int = 0, a_is_left: bool = True, raw: bool = False,
@@ -243,4 +282,4 @@ class McCnnAccurate:
         return (self.join(fl, fr, D, m, True, host=host), self.join(fr, fl, D, -(m + D) + 1, False, host=host))
 
 
-__all__ = ["McCnnAccurate", "FEATURES", "MAX_LAYERS", "MAX_FC_LAYERS", "MAX_UNITS", "MAX_DISPARITIES"]
+__all__ = ["McCnnAccurate", "PRECISIONS", "FEATURES", "MAX_LAYERS", "MAX_FC_LAYERS", "MAX_UNITS", "MAX_DISPARITIES"]

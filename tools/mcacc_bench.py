@@ -6,7 +6,13 @@ against (a) the f32-MFMA floors of the FLOP counts (2 K N per output) at 155 TFL
 running the same network in the same run: conv2d, then linear plane by plane.  One more line times
 the whole McCnnStereo.compute.  HIP events on one stream; every shape is warmed up first.
 
-    python tools/mcacc_bench.py [--out profiles/mcacc/mcacc_bench.jsonl] [--reps 10]
+--precision f32|bf16|both (the default f32 is the run above).  In bf16 mode the join's
+floor is the hidden layers' FLOP at the bf16 matrix rate (2.5 PFLOP/s dense, the specification) plus
+the projections' and the output unit's at the f32 rate; with "both" the two joins are timed in the
+same run, every bf16 line carries its speed-up over that run's f32 figure, and one line per size
+gives max and mean |bf16 - f32| of the similarity over the whole volume.
+
+    python tools/mcacc_bench.py [--out profiles/mcacc/mcacc_bench.jsonl] [--reps 10] [--precision both]
 
 One JSON line per measurement (times in ms: the median and the range of the repeats)."""
 import argparse
@@ -19,6 +25,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 MFMA_F32_TFLOPS = 155.0  # measured rate of the f32-input matrix instruction
+MFMA_BF16_TFLOPS = 2500.0  # dense bf16 rate of the specification
 
 
 def timed(fn, reps, warmup=2):
@@ -82,12 +89,15 @@ def main():
     ap.add_argument("--batches", default="1,2")
     ap.add_argument("--no-torch", action="store_true")
     ap.add_argument("--no-stereo", action="store_true")
+    ap.add_argument("--precision", choices=("f32", "bf16", "both"), default="f32")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("mcacc_bench needs the GPU: a CPU run gives no time")
     dev = torch.device("cuda", 0)
     L, F, U = args.layers, args.fc_layers, args.units
     m = sm.McCnnAccurate.random(L, F, U, 0)
+    precisions = ("f32", "bf16") if args.precision == "both" else (args.precision,)
+    nets = {p: m.with_precision(p) for p in precisions}
     ws = [torch.tensor(w, device=dev) for w in m.weights]
     bs = [torch.tensor(b, device=dev) for b in m.biases]
     fws = [torch.tensor(w, device=dev) for w in m.fc_weights]
@@ -122,9 +132,26 @@ def main():
                  ratio_to_mfma_floor=r["ms"] / floor(flop_feat), tflops=flop_feat / r["ms"] / 1e9)
             r = timed(lambda: m.join(fa, fb, 1), args.reps)
             emit(what="join_one_plane", **base, **r, ms_per_pair=r["ms"] / n, projection_mfma_floor_ms=floor(flop_proj))
-            r = timed(lambda: m.join(fa, fb, D), args.reps)
-            emit(what="join", **base, **r, ms_per_view=r["ms"] / n, mfma_floor_ms=floor(flop_proj + flop_score),
-                 ratio_to_mfma_floor=r["ms"] / floor(flop_proj + flop_score), tflops=(flop_proj + flop_score) / r["ms"] / 1e9)
+            flop_hidden = 2.0 * U * U * (F - 1) * cells
+            join_ms = {}
+            for p, net in nets.items():
+                r = timed(lambda: net.join(fa, fb, D), args.reps)
+                join_ms[p] = r["ms"]
+                if p == "f32":
+                    fl = floor(flop_proj + flop_score)
+                    emit(what="join", precision=p, **base, **r, ms_per_view=r["ms"] / n, mfma_floor_ms=fl,
+                         ratio_to_mfma_floor=r["ms"] / fl, tflops=(flop_proj + flop_score) / r["ms"] / 1e9)
+                else:
+                    fl = flop_hidden / (MFMA_BF16_TFLOPS * 1e12) * 1e3 + floor(flop_proj + flop_score - flop_hidden)
+                    extra = {"speedup_over_f32_same_run": join_ms["f32"] / r["ms"]} if "f32" in join_ms else {}
+                    emit(what="join", precision=p, **base, **r, ms_per_view=r["ms"] / n, mfma_floor_ms=fl,
+                         ratio_to_mfma_floor=r["ms"] / fl, tflops=(flop_proj + flop_score) / r["ms"] / 1e9, **extra)
+            if len(nets) == 2 and n == 1:
+                diff = (nets["bf16"].join(fa, fb, D) - nets["f32"].join(fa, fb, D)).abs()
+                ok = ~torch.isnan(diff)
+                emit(what="similarity_bf16_minus_f32", **base, max_abs=float(diff[ok].max()), mean_abs=float(diff[ok].mean()),
+                     cells=int(ok.sum()))
+                del diff, ok
             if not args.no_torch:
                 with torch.no_grad():
                     rt = timed(lambda: torch_features(a, ws, bs), args.reps)
@@ -135,9 +162,10 @@ def main():
                     del ta, tb
             del fa, fb
             if first and n == 1 and not args.no_stereo:
-                stereo = sm.McCnnStereo(m)
-                r = timed(lambda: stereo.compute(a[0], b[0], D), max(3, args.reps // 3), warmup=1)
-                emit(what="stereo_compute", **base, **r)
+                for p, net in nets.items():
+                    stereo = sm.McCnnStereo(net)
+                    r = timed(lambda: stereo.compute(a[0], b[0], D), max(3, args.reps // 3), warmup=1)
+                    emit(what="stereo_compute", precision=p, **base, **r)
             torch.cuda.empty_cache()
         first = False
 
