@@ -832,8 +832,11 @@ int sm_set_tuning(sm_ctx* ctx, int key, int value);
  * apart; each is normalised to zero mean and unit (unbiased) standard deviation, and a constant
  * image fails the call with SM_E_ARG.  H * W < 2^24.  Feature maps: float32 [n][H][W][64]
  * (channel last); device feature pointers (d_feat, d_feat_a, d_feat_b) must be 16-byte aligned
- * (SM_E_ARG otherwise).  Volumes: float32 [n][D][H][W], D in 1..256, any min_disparity.  The
- * device entry points run on the context's stream; the features wait for the images' sums (the
+ * (SM_E_ARG otherwise).  Volumes: float32 [n][D][H][W], D in 1..256, any min_disparity.  Rows:
+ * sm_mccnn_features_device (and sm_mccnn_features on it) takes H <= 524280, sm_mccnn_join_device
+ * (and the join and volume entry points on it) H <= 65535; more rows fail with SM_E_UNSUPPORTED
+ * and a message that states the limit, before anything is launched.
+ * The device entry points run on the context's stream; the features wait for the images' sums (the
  * check for a constant image) and for the upload of the grey-level tables, the join does not
  * wait.  The scratch buffers belong to the context: a caller that moves it to another stream
  * between calls orders the two streams itself. */
@@ -871,7 +874,9 @@ int sm_mccnn_join_host(const float* feat_a, const float* feat_b, int n, int H, i
  * Weights: w[0] float32 [112][1][3][3], w[i] [112][112][3][3], b[i] [112]; fw[0] [U][224],
  * fw[1..F-1] [U][U], fw[F] [1][U] (nn.Linear's [out][in]), fb[i] [U], fb[F] [1].  Images,
  * alignment, D, min_disparity and streams as for the fast net above; its weights in the same
- * context are not disturbed.  The scorer works through scratch buffers of the context in chunks of
+ * context are not disturbed.  Rows: sm_mcacc_features_device (and the features and volume entry
+ * points on it) takes H <= 131070 (SM_E_UNSUPPORTED beyond); sm_mcacc_join_device takes every H the
+ * pixel limit allows.  The scorer works through scratch buffers of the context in chunks of
  * cells (SM_TUNE_MCACC_CHUNK); their size is bounded and does not grow with H * W * D. */
 int sm_mcacc_set_weights(sm_ctx* ctx, int L, const float* const* w, const float* const* b, int F, int U,
                          const float* const* fw, const float* const* fb);

@@ -80,6 +80,8 @@ int sm_mccnn_features_device(sm_ctx* ctx, const uint8_t* d_gray, int n, size_t i
     if ((rc = mccnn_check_images(ctx, n, H, W)) != SM_OK) return rc;
     if ((rc = mccnn_check_strides(ctx, n, image_stride, H, W, row_stride)) != SM_OK) return rc;
     if ((rc = mccnn_check_aligned(ctx, d_feat, "d_feat")) != SM_OK) return rc;
+    // the convolutions' grid has a workgroup row per MC_TH image rows, at most 65535 of them
+    if (H > smk::MC_TH * 65535) return fail(ctx, SM_E_UNSUPPORTED, "mccnn: %d rows (at most 524280)", H);
     const int L = ctx->mccnn.L;
     if (L < 1) return fail(ctx, SM_E_ARG, "mccnn: no weights (sm_mccnn_set_weights comes first)");
     HIP_TRY(ctx, hipSetDevice(ctx->device));

@@ -7,12 +7,14 @@ import functools
 import numpy as np
 
 import stereo_match_amd as sm
-from mcacc_cases import SHAPES, image, model, same_bits, twin_features  # noqa: F401  (re-exported)
+from mcacc_cases import SHAPES, UNITS, UNITS_INTERLEAVED, image, model, same_bits, twin_features  # noqa: F401  (re-exported)
 
 C = 112
 
-# (rows, columns) of the integer feature maps; the first two are mccnn_cases.SHAPES' tiny and ragged
-GEOMETRY = {"tiny": (13, 45), "ragged": (37, 70), "narrow": (9, 19), "odd": (11, 37), "wide": (64, 256)}
+# (rows, columns) of the integer feature maps; the first two are mccnn_cases.SHAPES' tiny and ragged;
+# tall has more rows than a grid has workgroup rows (65535)
+GEOMETRY = {"tiny": (13, 45), "ragged": (37, 70), "narrow": (9, 19), "odd": (11, 37), "wide": (64, 256),
+            "tall": (65538, 2)}
 
 
 def bf16_round(x):

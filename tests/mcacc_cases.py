@@ -10,6 +10,12 @@ from mccnn_cases import SHAPES, image, same_bits  # noqa: F401  (re-exported)
 
 C = 112
 
+# every hidden width the scorer takes, and the same twelve from the ends inwards (384, 32, 352, 64,
+# ...): neither ascending nor descending, so one engine repacks its weights from larger to smaller
+# U and back
+UNITS = tuple(range(32, 385, 32))
+UNITS_INTERLEAVED = tuple(u for pair in zip(UNITS[::-1], UNITS) for u in pair)[:len(UNITS)]
+
 
 @functools.lru_cache(maxsize=None)
 def model(conv_layers=2, fc_layers=2, units=96, seed=0):

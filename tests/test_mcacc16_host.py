@@ -87,6 +87,62 @@ def test_dense_integer_scorer(F, U, bites):
     assert not Q.same_bits(Q.int_volume16(F, U, "tiny", 20, 0, True)[0], Q.int_volume16(F, U, "tiny", 20, 0, False)[0])
 
 
+def check_sweep_conditions(F, info):
+    """What makes a case of the width sweep (here and in test_gpu_mcacc_widths.py) say something:
+    every sum exact in float32, and with three or more layers operands the rounding changes, exact
+    ties among them.  With two layers the hidden operands are below 2^8 and nothing is rounded."""
+    assert 0 < info["peak"] < 2**24
+    if F >= 3:
+        assert max(info["changed"]) > 0 and info["ties"] > 0
+    else:
+        assert max(info["changed"]) == 0
+
+
+@pytest.mark.parametrize("U", Q.UNITS)
+@pytest.mark.parametrize("F", [2, 3, 4])
+def test_dense_integer_scorer_every_width(F, U):
+    """Every hidden width the scorer takes, on the 11 x 37 map with 6 planes from offset 1 (ragged
+    against the device's 32-column and 4-plane tiles): the raw bf16 twin equals the exact evaluation
+    in both roles."""
+    m = Q.dense_model(F, U)
+    fa, fb = Q.int_features("odd", 0), Q.int_features("odd", 1)
+    for left in (True, False):
+        want, info = Q.int_volume16(F, U, "odd", 6, 1, left)
+        check_sweep_conditions(F, info)
+        got = m.join(fa, fb, 6, 1, a_is_left=left, raw=True, host=True)
+        assert got.shape == (1,) + want.shape and Q.same_bits(got[0], want), int((got[0] != want).sum())
+    assert not Q.same_bits(Q.int_volume16(F, U, "odd", 6, 1, True)[0], Q.int_volume16(F, U, "odd", 6, 1, False)[0])
+
+
+def test_width_sweep_figures():
+    """The figures DESIGN.md §4.21 states for the sweep: the largest sum of magnitudes, and the
+    smallest share of a layer's operands the rounding changes at three or more layers."""
+    peaks, least = {}, 1.0
+    for F in (2, 3, 4):
+        for U in Q.UNITS:
+            for left in (True, False):
+                info = Q.int_volume16(F, U, "odd", 6, 1, left)[1]
+                peaks[F, U] = max(peaks.get((F, U), 0), info["peak"])
+                if F >= 3:
+                    least = min(least, max(info["changed"]))
+    top = max(peaks, key=peaks.get)
+    print(f"width sweep: largest peak {peaks[top]} at {top}, least changed share {least:.4f}")
+    assert top == (4, 352) and peaks[top] == 4544944  # the left role's; the right role's is 4301246
+    assert least >= 0.012
+
+
+def test_tall_integer_scorer():
+    """65538 rows of 2 columns, more rows than a grid has workgroup rows: the twins equal the exact
+    evaluation there, bf16 and (nothing being rounded at two layers) f32."""
+    fa, fb = Q.int_features("tall", 0), Q.int_features("tall", 1)
+    want, info = Q.int_volume16(2, 32, "tall", 2, 0)
+    check_sweep_conditions(2, info)
+    assert np.isnan(want[1, :, 0]).all() and np.isfinite(want[0]).all() and np.isfinite(want[1, :, 1]).all()
+    for precision in ("bf16", "f32"):
+        got = Q.dense_model(2, 32, precision).join(fa, fb, 2, 0, raw=True, host=True)
+        assert Q.same_bits(got[0], want)
+
+
 @pytest.mark.parametrize("F,U", [(1, 32), (2, 96), (4, 64)])
 def test_twin_is_its_chain(F, U):
     """Random float hidden layers: the twin equals sequential float32 additions of the exact

@@ -14,7 +14,8 @@ from stereo_match_amd import _lib
 SIGMOID_MAX_ULP = 2.4808  # 2.4807 at z = -16.635704
 
 
-@pytest.mark.parametrize("F,U", [(2, 32), (3, 96), (2, 96), (3, 32)])
+# 160 and 352: a partial 128-column tile of the device's dense layer behind full ones; 256: two full ones
+@pytest.mark.parametrize("F,U", [(2, 32), (3, 96), (2, 96), (3, 32), (3, 160), (2, 256), (3, 352)])
 def test_exact_integers(F, U):
     """Every partial sum is an integer below 2^24, so the float32 twin must give the int64 values
     exactly, whatever the order of its sums; swapped halves or the wrong role give other values."""
